@@ -11,15 +11,29 @@ dropout / channel masking / time mask off (as in the reference CPU baseline).
 One timed step = zero_grad + forward + loss + backward over
 ``--videos`` videos per rank (+ the gradient all-reduce for N>1), with the weights
 FIXED, so the data-dependent TDU segment counts S stay those of the initial weights
-(bench asserts they equal the CPU oracle's).  The reference train step's
+(``--full`` checks that they equal the CPU oracle's).  The reference train step's
 clip_grad_norm_(10) + Adam(lr 1e-4) (scripts/train.py:265-268) is timed separately
-afterwards and reported as the extra key ``train_step_with_adam`` (its updates move
+afterwards by ``--full`` and reported as the extra key ``train_step_with_adam`` (its updates move
 the weights and therefore S; the S it ends with is reported there).
 
-  python bench.py [--gpus N --steps K --warmup W]
-  python bench.py --config breakfast         # BASELINE configs[0]: vanilla FACT, T=512
-  python bench.py --config shipped           # havid_view0_lh_pt_holdout.yaml as shipped (training mode)
+  python bench.py [--gpus N --steps K --warmup W]    # the plain run: set up, warm up, time K steps, one JSON line
+  python bench.py --full                             # + rooflines, Adam leg, precision modes, DP schedule, CPU baseline
+  python bench.py --dump-outputs DIR                 # + the last timed step's outputs as DIR/<name>.npy
+  python bench.py --full --config breakfast          # BASELINE configs[0]: vanilla FACT, T=512
+  python bench.py --full --config shipped            # havid_view0_lh_pt_holdout.yaml as shipped (training mode)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run does only what the headline figure needs.  ``--full`` adds every other measurement and check:
+the sampled kernel-event rooflines (an extra untimed step counts the launches, the first timed step(s) carry
+the event pairs), the train step with clip_grad_norm_ + Adam, the other GEMM precision modes, the RCCL
+data-parallel schedule overhead and the CPU oracle baseline with its TDU segment check (``--adam-steps``,
+``--no-bf16``, ``--no-dp-overhead`` and ``--no-cpu-baseline`` trim a full run).
+
+``--dump-outputs DIR`` writes what a caller of the timed step receives from its LAST timed step (rank 0):
+the batch loss, every video's predictions and loss terms, every block's per-frame class logits, the TDU
+segment counts, and of the flat gradient buffer each parameter's sum and L2 norm plus a fixed seeded
+sample of its elements.  Weights, videos and the sample are seeded, so two builds run with the same
+arguments can be compared array by array.
 
 ``python bench.py --gpus N`` (N > 1, no launcher environment) starts the N ranks itself as a
 torchrun child before anything touches the GPU, and refuses (exit 2) when fewer than N GPUs are
@@ -525,6 +539,45 @@ def launch_ranks(n):
     return subprocess.call(cmd, env=env)
 
 
+GRAD_SAMPLE = 1 << 22       # --dump-outputs: gradient elements kept (the flat buffer is ~112 MB at the default dims)
+
+
+def dump_outputs(path, net, dp, loss, saves):
+    """--dump-outputs: what the caller of one timed step holds after it, as <path>/<name>.npy (float32 /
+    float64, ~30 MB at the default shape): loss, per video the predictions, loss terms and every block's
+    frame logits, the TDU segment counts, and the gradients (per-parameter sum and L2 norm in float64,
+    a seeded sample of GRAD_SAMPLE elements of the flat buffer)."""
+    os.makedirs(path, exist_ok=True)
+
+    def put(name, a, dtype=np.float32):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(np.asarray(a, dtype=dtype)))
+    torch.cuda.synchronize()
+    put("loss", [float(loss)], np.float64)
+    put("tdu_segments", video_segments(net), np.float64)
+    for v, save in enumerate(saves):
+        put(f"pred_v{v}", save["pred"])
+        put(f"loss_terms_v{v}", [save["loss"][k] for k in sorted(save["loss"])], np.float64)
+    for k, blk in enumerate(net.block_list):
+        recs = getattr(blk, "_vrec", None)   # lockstep batch: every video; else the last video run
+        z = [r["frame_clogit"] for r in recs] if recs else [blk.frame_clogit]
+        for v, t in enumerate(z):
+            put(f"frame_clogit_b{k}_v{v}", t.detach().float().reshape(t.shape[0], -1).cpu().numpy())
+    flat = dp.flat.detach()
+    g64 = flat.double()
+    sums, norms, off = [], [], 0
+    for p in dp.params:
+        n = p.numel()
+        sums.append(g64[off:off + n].sum())
+        norms.append(g64[off:off + n].norm())
+        off += n
+    put("grad_param_sum", torch.stack(sums).cpu().numpy(), np.float64)
+    put("grad_param_l2", torch.stack(norms).cpu().numpy(), np.float64)
+    if flat.numel() > GRAD_SAMPLE:
+        idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:GRAD_SAMPLE].sort().values
+        flat = flat[idx.to(flat.device)]
+    put("grad_sample", flat.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -539,12 +592,20 @@ def main():
     ap.add_argument("--data", choices=["seg10", "iid"], default="seg10",
                     help="seg10: the headline's synthetic videos; iid: the stress input (features i.i.d. N(0, 1), "
                          "thousands of TDU segments, BiGRU-bound)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: kernel-event rooflines, "
+                         "the Adam train step, the other precision modes, the DP schedule overhead, the CPU "
+                         "oracle baseline and its TDU segment check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (loss, predictions, frame logits, gradient "
+                         "sums / norms / sample) as DIR/<name>.npy")
     ap.add_argument("--adam-steps", type=int, default=None,
-                    help="extra timed steps with clip_grad_norm_ + Adam after the fixed-weight steps")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-bf16", action="store_true", help="skip the extra precision-mode measurements (N=1 only)")
+                    help="--full: extra timed steps with clip_grad_norm_ + Adam after the fixed-weight steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle baseline")
+    ap.add_argument("--no-bf16", action="store_true",
+                    help="--full: skip the extra precision-mode measurements (N=1 only)")
     ap.add_argument("--no-dp-overhead", action="store_true",
-                    help="skip the N=1 RCCL measurement of the data-parallel bucket schedule")
+                    help="--full: skip the N=1 RCCL measurement of the data-parallel bucket schedule")
     ap.add_argument("--prec", choices=["default", "fp32s", "fp32"], default="default",
                     help="GEMM arithmetic of the headline: the library default, fp32s (fp32 by a 3-piece bf16 split "
                          "on the bf16 matrix cores) or fp32 (f32 MFMA)")
@@ -552,7 +613,10 @@ def main():
     cfg, D, C, T_def, vids_def, clip, metric = workload(args.config)
     T = args.T or T_def
     nv = args.videos or vids_def
-    adam_steps = args.steps if args.adam_steps is None else args.adam_steps
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    full = args.full
+    adam_steps = 0 if not full else args.steps if args.adam_steps is None else args.adam_steps
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus))
@@ -589,11 +653,15 @@ def main():
         seqs.append(torch.from_numpy(f).to(dev))
         labels.append(torch.from_numpy(l_).to(dev))
 
-    def step():
+    kept = []     # (loss, saves) of the step --dump-outputs writes
+
+    def step(keep=False):
         dp.zero_grad()
-        loss, _ = net(seqs, labels, compute_loss=True)
+        loss, saves = net(seqs, labels, compute_loss=True)
         loss.backward()
         dp.finish_gradients()           # bucket all-reduces (mean) for N>1
+        if keep:
+            kept[:] = [loss.detach(), saves]
         return loss
 
     for _ in range(args.warmup):
@@ -612,22 +680,26 @@ def main():
     # (FX_BENCH_PROF_STEPS: steps to sample; the durations agree with the all-steps sampling).  The event
     # capacity of each kind is its launch count in one step, counted on an untimed extra warm-up step,
     # times the sampled steps -- so no event pair spills into the later timed steps.
+    # All of it is --full only: a plain run times its steps with no event pairs in them.
     psteps = min(args.steps, int(os.environ.get("FX_BENCH_PROF_STEPS", 1)))
     kinds = [0, 1, 2] + list(X2Y_KINDS) + [FRL_KIND] + list(XATTN_KINDS)
-    for kind in kinds:
-        native.check(lib.fx_prof_enable(kind, 4096), "fx_prof_enable")
-    step()
-    per_step = {kind: prof_collect(lib, kind).calls for kind in kinds}
-    lib.fx_prof_disable()
-    for kind in kinds:
-        if per_step[kind] > 0:
-            native.check(lib.fx_prof_enable(kind, per_step[kind] * psteps), "fx_prof_enable")
+    per_step = dict.fromkeys(kinds, 0)
+    if full:
+        for kind in kinds:
+            native.check(lib.fx_prof_enable(kind, 4096), "fx_prof_enable")
+        step()
+        per_step = {kind: prof_collect(lib, kind).calls for kind in kinds}
+        lib.fx_prof_disable()
+        for kind in kinds:
+            if per_step[kind] > 0:
+                native.check(lib.fx_prof_enable(kind, per_step[kind] * psteps), "fx_prof_enable")
+    dump_at = args.steps - 1 if (args.dump_outputs and rank == 0) else -1
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    for i in range(args.steps):
+        step(i == dump_at)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -641,12 +713,16 @@ def main():
     x2y_prof = {name: collect(kind) for kind, name in X2Y_KINDS.items()}
     frl_prof = collect(FRL_KIND)
     xattn_prof = {name: collect(kind) for kind, name in XATTN_KINDS.items()}
-    lib.fx_prof_disable()
+    if full:
+        lib.fx_prof_disable()
     S_after = video_segments(net)
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
+    if kept:        # before anything below runs further steps: the last timed step's outputs
+        dump_outputs(args.dump_outputs, net, dp, *kept)
+        log(f"[rank {rank}] outputs of timed step {args.steps} written to {args.dump_outputs}")
 
     # the reference train step (clip_grad_norm_ + Adam), timed right after the fixed-weight steps (same
     # device state); the weights are restored afterwards, so the precision modes below compare
@@ -685,7 +761,7 @@ def main():
     # (FX_PREC_BF16, fp32 accumulation / storage), its frame-logit deviation from the fp32 path on the
     # same weights and videos, and its TDU segment counts (N=1 only; the headline stays fp32)
     bf16 = other = None
-    if world == 1 and not args.no_bf16:
+    if full and world == 1 and not args.no_bf16:
         from factmx import functional as fxf
         bf16 = bf16_mode(net, step, sum(Ts), args.steps, args.warmup, fxf)
         # the other fp32 arithmetic (f32 MFMA when the headline runs the split, and vice versa)
@@ -693,7 +769,7 @@ def main():
                           "fp32" if headline_prec == "fp32s" else "fp32s")
 
     dp_sched = None
-    if world == 1 and not args.no_dp_overhead:
+    if full and world == 1 and not args.no_dp_overhead:
         try:
             dp_sched = dp_schedule_overhead(net, seqs, labels, args.steps)
         except Exception as e:          # reported, never fatal for the headline line
@@ -701,7 +777,9 @@ def main():
 
     frames = world * sum(Ts) * args.steps
     value = frames / elapsed
-    if rank == 0:
+
+    def rooflines():
+        """--full: the roofline keys of the result line, from the event pairs sampled in the timed region."""
         avg_ms = conv_prof.bracket_ms / max(conv_prof.calls, 1)
         flops_per_launch = conv_prof.flops / max(conv_prof.calls, 1)
         achieved = flops_per_launch / (avg_ms * 1e-3) / 1e12 if avg_ms > 0 else 0.0
@@ -754,6 +832,12 @@ def main():
                     r["traffic_shape"] = "2 x 4096 frames x 32 tokens, Hd 512 (= this line's calls)"
                     if default_shape:
                         trace_basis(r, name, r["bytes_per_launch"], HBM_PEAK_GBS, 1e9)
+        return dict(roofline=roofline, roofline_attention=roofline_attention,
+                    roofline_xattn_gemm={name: gemm_roofline(name, v, F32_MFMA_PEAK_TFLOPS)
+                                         for name, v in xattn_prof.items()},
+                    roofline_conv_gemm=conv_roofline, roofline_fused_layer=frl_roofline)
+
+    if rank == 0:
         line = dict(metric=metric, value=round(value, 1), unit="frames/s", n_gpus=world, steps=args.steps,
                     warmup=args.warmup, ms_per_step=round(1e3 * elapsed / args.steps, 3), higher_is_better=True,
                     scaling="weak", vs_baseline=None, dtype="fp32", data="synthetic",
@@ -768,14 +852,12 @@ def main():
                                 videos_per_rank=nv, global_batch=world * nv, seq_len=T,
                                 parallelism=f"dp{world}", weights="fixed (no optimizer update in the timed steps)",
                                 tdu_segments=S, tdu_segments_after_timing=S_after),
-                    roofline=roofline, roofline_attention=roofline_attention,
-                    roofline_xattn_gemm={name: gemm_roofline(name, v, F32_MFMA_PEAK_TFLOPS)
-                                         for name, v in xattn_prof.items()},
-                    roofline_conv_gemm=conv_roofline, roofline_fused_layer=frl_roofline, train_step_with_adam=adam,
-                    bf16_mode=bf16, dp_schedule=dp_sched)
+                    full=full)
+        if full:
+            line.update(rooflines(), train_step_with_adam=adam, bf16_mode=bf16, dp_schedule=dp_sched)
         if other is not None:
             line["fp32_f32mfma_mode" if headline_prec == "fp32s" else "fp32_split_mode"] = other
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             cb, step_flops, S_oracle = cpu_baseline(args.config, Ts, seeds, data=args.data)
             line["cpu_baseline"] = cb
             line["tdu_segments_oracle"] = S_oracle
@@ -787,7 +869,7 @@ def main():
             line["step_gflop_per_video"] = round(step_flops / nv / 1e9, 2)
             if S_oracle != S and args.config != "shipped":
                 log(f"WARNING: GPU TDU segments {S} differ from the oracle's {S_oracle}")
-        else:
+        elif full:
             line["cpu_baseline"] = None
         print(json.dumps(line), flush=True)
     if world > 1:

@@ -5,6 +5,7 @@ import os
 import numpy as np
 import torch
 
+import fixture_io
 import paramgen as pg
 from factmx.configs import get_cfg_defaults
 
@@ -12,7 +13,8 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def load_fixture(name):
-    return np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
+    """tests/golden/<name>.npz, or its <name>.<i>.npz parts, as one mapping (fixture_io)."""
+    return fixture_io.load_fixture(name, GOLDEN)
 
 
 def tiny_meta(fx):

@@ -7,7 +7,7 @@ IFS=';' read -ra VS <<< "${VARIANTS:-base=}"
 for r in $(seq 1 ${ROUNDS:-3}); do
   for v in "${VS[@]}"; do
     name=${v%%=*}; envs=${v#*=}
-    env $envs timeout -k 10 300 python bench.py --steps ${STEPS:-20} --warmup 5 --adam-steps 0 --no-cpu-baseline --no-bf16 --no-dp-overhead ${BENCH_ARGS:-} > $O/$name.$r.json 2> $O/$name.$r.err || { tail -5 $O/$name.$r.err; exit 3; }
+    env $envs timeout -k 10 300 python bench.py --full --steps ${STEPS:-20} --warmup 5 --adam-steps 0 --no-cpu-baseline --no-bf16 --no-dp-overhead ${BENCH_ARGS:-} > $O/$name.$r.json 2> $O/$name.$r.err || { tail -5 $O/$name.$r.err; exit 3; }
     python - "$O/$name.$r.json" "$name" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -8,7 +8,7 @@ IFS=';' read -ra VS <<< "${VARIANTS:-base=}"
 for v in "${VS[@]}"; do
   name=${v%%=*}; envs=${v#*=}
   for e in $envs; do export "$e"; done
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/$name -o run --output-format csv -- python bench.py --steps 10 --warmup 3 --adam-steps 0 --no-cpu-baseline --no-bf16 --no-dp-overhead > $O/$name.json 2> $O/$name.log || { tail -20 $O/$name.log; exit 4; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/$name -o run --output-format csv -- python bench.py --full --steps 10 --warmup 3 --adam-steps 0 --no-cpu-baseline --no-bf16 --no-dp-overhead > $O/$name.json 2> $O/$name.log || { tail -20 $O/$name.log; exit 4; }
   for e in $envs; do unset "${e%%=*}"; done
   echo "== $name"
   python tools/step_map.py $(find $O/$name -name "*kernel_trace.csv") 8 | head -20

@@ -11,11 +11,11 @@ if [ "$T" != "none" ]; then
   tail -3 $O/pytest.log
 fi
 if [ "${BENCH:-1}" = "1" ]; then
-  timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 3; }
+  timeout -k 10 600 python bench.py --full ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 3; }
   tail -1 $O/bench.json | cut -c1-400
 fi
 if [ "${PROF:-1}" = "1" ]; then
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python bench.py --steps 10 --warmup 3 --adam-steps 0 --no-cpu-baseline --no-bf16 --no-dp-overhead ${BENCH_ARGS:-} > $O/prof.json 2> $O/prof.log || { tail -20 $O/prof.log; exit 4; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python bench.py --full --steps 10 --warmup 3 --adam-steps 0 --no-cpu-baseline --no-bf16 --no-dp-overhead ${BENCH_ARGS:-} > $O/prof.json 2> $O/prof.log || { tail -20 $O/prof.log; exit 4; }
   # 3 warm-up + 1 calibration (event counts) + 10 timed steps = 14 steps in the profiled command
   python tools/kstats.py $(find $O/prof -name "*kernel_stats.csv") 14 40 > $O/kstats.txt
   python tools/step_map.py $(find $O/prof -name "*kernel_trace.csv") 10 > $O/step_map.txt

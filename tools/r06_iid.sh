@@ -9,6 +9,6 @@ for p in ${PATHS:-planner tiled direct}; do
 done
 cat $O/seg${SWEEP}_*.txt | grep -v amdgpu.ids
 if [ "${IID:-0}" = "1" ]; then
-  timeout -k 10 900 python bench.py --data iid --steps 3 --warmup 1 --adam-steps 0 --no-bf16 --no-dp-overhead > $O/bench_iid.json 2> $O/bench_iid.err || { tail -20 $O/bench_iid.err; exit 4; }
+  timeout -k 10 900 python bench.py --full --data iid --steps 3 --warmup 1 --adam-steps 0 --no-bf16 --no-dp-overhead > $O/bench_iid.json 2> $O/bench_iid.err || { tail -20 $O/bench_iid.err; exit 4; }
   tail -1 $O/bench_iid.json | cut -c1-400
 fi
