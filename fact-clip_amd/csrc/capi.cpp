@@ -380,6 +380,10 @@ struct MstcnLayout {
 #endif
 int defer_split_impl(int rows) { return std::max(1, std::min(FX_DEFER_SPLIT_BUILD, rows / 512)); }
 
+// groups of the dilated convs: fx_mstcn_params.ngroup / fx_mstcn2_params.ngroup (0 and 1: dense; an invalid
+// count sizes as dense -- the entry points refuse it)
+int mstcn_groups(int ngroup, int F) { return ngroup > 1 && F > 0 && F % ngroup == 0 ? ngroup : 1; }
+
 MstcnLayout mstcn_layout(const fx_mstcn_params* p, int rows) {
   MstcnLayout L{};
   const long long F = p->F;
@@ -391,15 +395,18 @@ MstcnLayout mstcn_layout(const fx_mstcn_params* p, int rows) {
   L.xh = L.z + NL * L.rowsF;                 // LN xhat_i
   L.rs = L.xh + (p->layernorm ? NL * L.rowsF : 0);
   L.wbs = L.rs + (p->layernorm ? (long long)NL * rows : 0);   // dX-packed conv weights (fwd packs, bwd reads)
-  const long long wsz = 3 * F * F;
+  // grouped dilated convs (ngroup > 1): conv weight blocks of 3 F cg floats, no fused layers
+  const int ng = mstcn_groups(p->ngroup, p->F);
+  const bool fl = p->fused_layers && ng == 1;
+  const long long wsz = 3 * F * (F / ng);
   L.wpts = L.wbs + NL * wsz;                 // transposed 1x1 weights (fwd packs, bwd dZ GEMM reads)
   L.wk1b = L.wpts + NL * F * F;              // fused layers: the backward chain's weights (the two above) in
-  L.wk2b = L.wk1b + (p->fused_layers ? NL * wsz : 0);   // MFMA fragment order, packed by the forward
-  L.total_saved = L.wk2b + (p->fused_layers ? NL * F * F : 0);
+  L.wk2b = L.wk1b + (fl ? NL * wsz : 0);     // MFMA fragment order, packed by the forward
+  L.total_saved = L.wk2b + (fl ? NL * F * F : 0);
   L.wf = 0;
   L.wk1 = L.wf + NL * wsz;                   // fused layers: conv weights in MFMA fragment order
-  L.wk2 = L.wk1 + (p->fused_layers ? NL * wsz : 0);   // ... and the 1x1 weights
-  L.buf0 = L.wk2 + (p->fused_layers ? NL * F * F : 0);
+  L.wk2 = L.wk1 + (fl ? NL * wsz : 0);       // ... and the 1x1 weights
+  L.buf0 = L.wk2 + (fl ? NL * F * F : 0);
   L.buf1 = L.buf0 + L.rowsF;
   L.buf2 = L.buf1 + L.rowsF;
   L.buf3 = L.buf2 + L.rowsF;                 // backward: third dH buffer, second dZ buffer (side stream)
@@ -415,6 +422,7 @@ MstcnLayout mstcn_layout(const fx_mstcn_params* p, int rows) {
   sp = std::max(sp, split_ws(rows, p->F, p->cout));           // dH_L
   if (p->in_map) sp = std::max(sp, split_ws(rows, p->cin, p->F));
   sp = std::max(sp, layernorm_bwd_ws_floats(rows, p->F));
+  if (ng > 1) sp = std::max(sp, gconv_dw_ws_floats(rows, p->F, ng));   // grouped conv dW partials
   L.split2 = L.split + sp;                   // split-K partials of the main stream's GEMMs
   L.colsum = L.split2 + sp;
   long long cs = colsum_workspace_floats(rows, std::max(std::max(p->F, p->cout), p->cin));
@@ -433,6 +441,15 @@ MstcnLayout mstcn_layout(const fx_mstcn_params* p, int rows) {
 
 int pack_conv_weights(const fx_mstcn_params* p, float* ws, float* wbdst, float* wptdst, const MstcnLayout& L,
                       hipStream_t s) {
+  const int ng = mstcn_groups(p->ngroup, p->F);
+  if (ng > 1) {   // grouped: per-group tap-major images (conv_grouped.hip) + the transposed 1x1 weights
+    const long long gsz = gconv_packed_floats(p->F, ng);
+    std::vector<GPackJob> J;
+    for (int l = 0; l < p->num_layers; ++l)
+      J.push_back({p->w_dil[l], ws + L.wf + l * gsz, wbdst + l * gsz, p->w_pw[l],
+                   wptdst ? wptdst + (long long)l * p->F * p->F : nullptr});
+    return J.empty() ? FX_OK : launch_gconv_pack(J.data(), (int)J.size(), p->F, ng, s);
+  }
   PackArgs a{};
   a.F = p->F;
   const long long wsz = 3LL * p->F * p->F;
@@ -467,7 +484,7 @@ int launch_frag_jobs(const std::vector<FragJob>& J, hipStream_t s) {
 
 // whether fx_mstcn_fwd ran the fused layers (and so packed the backward chain's weights into `saved`)
 bool mstcn_fwd_fused(const fx_mstcn_params* p, int nvid, bool ragged, int rows, const float* saved) {
-  return p->fused_layers && !p->layernorm && frl_supported(p->F, saved, p->F, p->F) && (!ragged || nvid <= 16) &&
+  return p->fused_layers && p->ngroup <= 1 && !p->layernorm && frl_supported(p->F, saved, p->F, p->F) && (!ragged || nvid <= 16) &&
          (p->fused_layers == 2 || frl_fills_device(rows));
 }
 
@@ -672,10 +689,12 @@ int fx_mstcn_fwd(const fx_mstcn_params* p, const float* x, long long ldx, int T,
   hipStream_t s = (hipStream_t)stream;
   FX_REQUIRE(p && p->num_layers >= 0 && p->num_layers <= 32, "mstcn: 0..32 layers");
   FX_REQUIRE(p->in_map || p->cin == p->F, "mstcn: in_map=0 needs cin == F");
+  FX_TRY(gconv_check(p->F, p->ngroup, "mstcn"));
   const Seqs q{T, nvid, p->seq_off};
   FX_TRY(check_seqs(q));
   const int rows = q.rows();
   const int F = p->F;
+  const int ng = mstcn_groups(p->ngroup, F);
   const MstcnLayout L = mstcn_layout(p, rows);
   FX_TRY(pack_conv_weights(p, workspace, saved + L.wbs, saved + L.wpts, L, s));
   if (L.rows_pad > rows && p->num_layers > 0)   // pad rows of h_0 .. h_NL, z_0 .. z_NL-1 (adjacent slots)
@@ -716,13 +735,20 @@ int fx_mstcn_fwd(const fx_mstcn_params* p, const float* x, long long ldx, int T,
       continue;
     }
     // z = relu(dilated_conv(h) + b)      (basic.py:158)
-    fx_gemm_desc d = gemm_desc(rows, F, 3 * F, conv_operand(hi, F, F, layer_dilation(p, i), 1, q, false),
-                               op_rows(workspace + L.wf + (long long)i * 3 * F * F, 3 * F), zi, F);
-    d.bias = p->b_dil[i];
-    d.relu = 1;
-    prof_begin(0, s);
-    FX_TRY(launch_gemm(d, s));
-    prof_end(0, s, 2.0 * rows * F * 3.0 * F, 4.0 * (2.0 * rows * F + 3.0 * F * F));
+    if (ng > 1) {   // grouped conv kernel: K = 3 F / ng per output column
+      prof_begin(0, s);
+      FX_TRY(launch_gconv(hi, F, rows, T, q.nvid, q.off, F, ng, layer_dilation(p, i), 1,
+                          workspace + L.wf + i * gconv_packed_floats(F, ng), p->b_dil[i], 1, nullptr, 0, 0, zi, F, s));
+      prof_end(0, s, 2.0 * rows * F * 3.0 * (F / ng), 4.0 * (2.0 * rows * F + 3.0 * F * (F / ng)));
+    } else {
+      fx_gemm_desc d = gemm_desc(rows, F, 3 * F, conv_operand(hi, F, F, layer_dilation(p, i), 1, q, false),
+                                 op_rows(workspace + L.wf + (long long)i * 3 * F * F, 3 * F), zi, F);
+      d.bias = p->b_dil[i];
+      d.relu = 1;
+      prof_begin(0, s);
+      FX_TRY(launch_gemm(d, s));
+      prof_end(0, s, 2.0 * rows * F * 3.0 * F, 4.0 * (2.0 * rows * F + 3.0 * F * F));
+    }
     // h' = h + z . Wpw^T + b   [then LN]   (basic.py:159-169)
     float* u = p->layernorm ? workspace + L.buf0 : hn;
     fx_gemm_desc e = gemm_desc(rows, F, F, op_rows(zi, F), op_rows(p->w_pw[i], F), u, F);
@@ -752,15 +778,18 @@ int fx_mstcn_bwd(const fx_mstcn_params* p, const fx_mstcn_grads* g, const float*
   const MstcnLayout L = mstcn_layout(p, rows);
   float* ws = workspace;
   FX_REQUIRE(p->dropout >= 0.f && p->dropout < 1.f, "mstcn: dropout must be in [0, 1)");
+  FX_TRY(gconv_check(F, p->ngroup, "mstcn"));
+  // grouped dilated convs: the per-layer schedule below with the grouped kernels (no fused chain, no batched dW)
+  const int ng = mstcn_groups(p->ngroup, F);
   const bool drop = p->dropout > 0.f;
   // deferred batched weight gradients (below); with training dropout the chain also keeps every layer's
   // masked dB_i for the 1x1 weight gradient.  (The input block's stack is the LAST work of the backward
   // pass, so its batched dW runs after the chain with nothing left to overlap, a ~0.7 ms side-stream tail;
   // giving it the per-layer schedule, or launching the upper layers' dW mid-chain, measured even: the
   // overlapped GEMMs slow the chain by as much, rounds 3 and 5)
-  const bool defer = !p->layernorm && NL > 0 && mstcn_defer_ok(p, g);
+  const bool defer = !p->layernorm && NL > 0 && ng == 1 && mstcn_defer_ok(p, g);
   // Fused chain (no LayerNorm, <= 16 ragged videos, FX_MSTCN_FUSED=1; dropout on the deferred schedule): see below
-  const bool fchain = p->fused_layers && !p->layernorm && (!drop || defer) && NL > 0 &&
+  const bool fchain = p->fused_layers && ng == 1 && !p->layernorm && (!drop || defer) && NL > 0 &&
                       frl_supported(F, ws + L.buf0, F, F) && (!q.off || q.nvid <= 16) &&
                       (p->fused_layers == 2 || frl_fills_device(rows));
   // the dX-packed conv weights and the transposed 1x1 weights come from the forward (saved); the fused
@@ -832,6 +861,9 @@ int fx_mstcn_bwd(const fx_mstcn_params* p, const fx_mstcn_grads* g, const float*
   // Zb[(NL - 1 - i) % 3]; a kernel overwriting a buffer first waits for the side stream's layer
   // that last read it (layer i + 2 for both).
   auto conv_dw = [&](int i, const float* dZi) -> int {
+    if (ng > 1)   // one launch over every video and group, partials in the side stream's split region
+      return launch_gconv_dw(dZi, F, saved + L.h + i * L.rowsF, F, rows, T, q.nvid, q.off, F, ng,
+                             layer_dilation(p, i), g->w_dil[i], g->b_dil[i], spl, sd);
     return per_video(q, [&](int r0, int nr, const Seqs& qv) -> int {
       fx_operand b = conv_operand(saved + L.h + i * L.rowsF + (long long)r0 * F, F, F, layer_dilation(p, i), 1, qv,
                                   true);
@@ -1018,13 +1050,20 @@ int fx_mstcn_bwd(const fx_mstcn_params* p, const fx_mstcn_grads* g, const float*
         dHn = Hb[(step + 1) % 3];
         FX_TRY(wait_side(i + 2));     // that buffer was gU of layer i + 2
       }
-      fx_gemm_desc d = gemm_desc(rows, F, 3 * F, conv_operand(dZ, F, F, layer_dilation(p, i), -1, q, false),
-                                 op_rows(wbp + (long long)i * 3 * F * F, 3 * F), dHn, F);
-      d.resid = gU;
-      d.ld_resid = F;
-      prof_begin(0, s);
-      FX_TRY(launch_gemm(d, s));
-      prof_end(0, s, 2.0 * rows * F * 3.0 * F, 4.0 * (3.0 * rows * F + 3.0 * F * F));
+      if (ng > 1) {
+        prof_begin(0, s);
+        FX_TRY(launch_gconv(dZ, F, rows, T, q.nvid, q.off, F, ng, layer_dilation(p, i), -1,
+                            wbp + i * gconv_packed_floats(F, ng), nullptr, 0, gU, F, 0, dHn, F, s));
+        prof_end(0, s, 2.0 * rows * F * 3.0 * (F / ng), 4.0 * (3.0 * rows * F + 3.0 * F * (F / ng)));
+      } else {
+        fx_gemm_desc d = gemm_desc(rows, F, 3 * F, conv_operand(dZ, F, F, layer_dilation(p, i), -1, q, false),
+                                   op_rows(wbp + (long long)i * 3 * F * F, 3 * F), dHn, F);
+        d.resid = gU;
+        d.ld_resid = F;
+        prof_begin(0, s);
+        FX_TRY(launch_gemm(d, s));
+        prof_end(0, s, 2.0 * rows * F * 3.0 * F, 4.0 * (3.0 * rows * F + 3.0 * F * F));
+      }
       if (p->layernorm) {
         if (dHn != dH) std::swap(dH, dU);   // dH now holds dH_i
       } else {
@@ -1069,7 +1108,8 @@ Mstcn2Layout mstcn2_layout(const fx_mstcn2_params* p, int rows) {
   L.f = 0;
   L.cat = L.f + (NL + 1) * L.rowsF;
   L.r = L.cat + 2 * NL * L.rowsF;
-  const long long wsz = 3 * F * F;
+  const int ng = mstcn_groups(p->ngroup, p->F);
+  const long long wsz = 3 * F * (F / ng);   // (grouped dilated convs: 3 F cg per conv)
   L.wb1 = L.r + NL * L.rowsF;
   L.wb2 = L.wb1 + NL * wsz;
   L.total_saved = L.wb2 + NL * wsz;
@@ -1093,6 +1133,7 @@ Mstcn2Layout mstcn2_layout(const fx_mstcn2_params* p, int rows) {
     sb = std::max(sb, split_ws(F, 2 * F + 1, rows, nb));
     sb = std::max(sb, split_ws(F, 3 * F + 1, rows, nb));
   }
+  if (ng > 1) sb = std::max(sb, gconv_dw_ws_floats(rows, p->F, ng));   // grouped conv dW partials
   L.total_ws = L.bsl + sb;
   return L;
 }
@@ -1104,7 +1145,13 @@ int mstcn2_dil(const fx_mstcn2_params* p, int e) {   // dil_factor^e
   return (int)d;
 }
 
-int pack_conv_set(const float* const* w, int NL, int F, float* wf, float* wb, hipStream_t s) {
+int pack_conv_set(const float* const* w, int NL, int F, int ng, float* wf, float* wb, hipStream_t s) {
+  if (ng > 1) {   // grouped: per-group tap-major images (conv_grouped.hip)
+    const long long gsz = gconv_packed_floats(F, ng);
+    std::vector<GPackJob> J;
+    for (int l = 0; l < NL; ++l) J.push_back({w[l], wf + l * gsz, wb + l * gsz, nullptr, nullptr});
+    return launch_gconv_pack(J.data(), NL, F, ng, s);
+  }
   PackArgs a{};
   a.F = F;
   const long long wsz = 3LL * F * F;
@@ -1142,14 +1189,17 @@ int fx_mstcn2_fwd(const fx_mstcn2_params* p, const float* x, long long ldx, int 
   FX_REQUIRE(p->in_map || p->cin == p->F, "mstcn2: in_map=0 needs cin == F");
   FX_REQUIRE(p->dropout >= 0.f && p->dropout < 1.f, "mstcn2: dropout must be in [0, 1)");
   FX_REQUIRE(saved && workspace && y, "mstcn2: bad arguments");
+  FX_TRY(gconv_check(p->F, p->ngroup, "mstcn2"));
   const Seqs q{T, nvid, p->seq_off};
   FX_TRY(check_seqs(q));
   const int rows = q.rows(), F = p->F, NL = p->num_layers;
+  const int ng = mstcn_groups(p->ngroup, F);
+  const long long gsz = gconv_packed_floats(F, ng);
   const Mstcn2Layout L = mstcn2_layout(p, rows);
   float* ws = workspace;
   if (NL > 0) {   // forward images into the workspace, dX images into `saved` for the backward
-    FX_TRY(pack_conv_set(p->w_d1, NL, F, ws + L.wf1, saved + L.wb1, s));
-    FX_TRY(pack_conv_set(p->w_d2, NL, F, ws + L.wf2, saved + L.wb2, s));
+    FX_TRY(pack_conv_set(p->w_d1, NL, F, ng, ws + L.wf1, saved + L.wb1, s));
+    FX_TRY(pack_conv_set(p->w_d2, NL, F, ng, ws + L.wf2, saved + L.wb2, s));
   }
   float* f0 = saved + L.f;
   if (p->in_map) {
@@ -1167,7 +1217,15 @@ int fx_mstcn2_fwd(const fx_mstcn2_params* p, const float* x, long long ldx, int 
     // (no torch.cat)   (basic.py:276)
     // (one batch-2 launch: batch h takes conv h's dilation, packed weights, bias and output half --
     // at Breakfast's 2048 rows the pair fills the chip with 128x64 tiles where one conv could not)
-    {
+    if (ng > 1) {   // grouped: one grouped-conv launch per dilated conv, each into its half of cat
+      for (int h = 0; h < 2; ++h) {
+        prof_begin(0, s);
+        FX_TRY(launch_gconv(fi, F, rows, T, q.nvid, q.off, F, ng, mstcn2_dil(p, h == 0 ? NL - 1 - i : i), 1,
+                            ws + (h == 0 ? L.wf1 : L.wf2) + i * gsz, h == 0 ? p->b_d1[i] : p->b_d2[i], 0, nullptr, 0,
+                            0, cat + h * F, 2 * F, s));
+        prof_end(0, s, 2.0 * rows * F * 3.0 * (F / ng), 4.0 * (2.0 * rows * F + 3.0 * F * (F / ng)));
+      }
+    } else {
       fx_gemm_desc d = gemm_desc(rows, F, 3 * F, conv_operand(fi, F, F, mstcn2_dil(p, NL - 1 - i), 1, q, false),
                                  op_rows(ws + L.wf1 + (long long)i * 3 * F * F, 3 * F), cat, 2 * F);
       d.batch = 2;
@@ -1199,9 +1257,12 @@ int fx_mstcn2_bwd(const fx_mstcn2_params* p, const fx_mstcn2_grads* g, const flo
                   void* stream) {
   hipStream_t s = (hipStream_t)stream;
   FX_REQUIRE(p && g && saved && workspace && dy, "mstcn2 bwd: bad arguments");
+  FX_TRY(gconv_check(p->F, p->ngroup, "mstcn2"));
   const Seqs q{T, nvid, p->seq_off};
   FX_TRY(check_seqs(q));
   const int rows = q.rows(), F = p->F, NL = p->num_layers;
+  const int ng = mstcn_groups(p->ngroup, F);
+  const long long gsz = gconv_packed_floats(F, ng);
   const Mstcn2Layout L = mstcn2_layout(p, rows);
   float* ws = workspace;
   SideStream* ss = side_stream();
@@ -1241,6 +1302,14 @@ int fx_mstcn2_bwd(const fx_mstcn2_params* p, const fx_mstcn2_grads* g, const flo
     float* dFn = Hb[(NL - i) & 1];
     for (int h = 0; h < 2; ++h) {
       const int dil = h == 0 ? mstcn2_dil(p, NL - 1 - i) : mstcn2_dil(p, i);
+      if (ng > 1) {   // grouped: conv_d1's pass writes gF + conv^T(dA), conv_d2's adds conv^T(dB)
+        prof_begin(0, s);
+        FX_TRY(launch_gconv(dCat + h * F, 2 * F, rows, T, q.nvid, q.off, F, ng, dil, -1,
+                            saved + (h == 0 ? L.wb1 : L.wb2) + i * gsz, nullptr, 0, h == 0 ? gF : nullptr, F, h != 0,
+                            dFn, F, s));
+        prof_end(0, s, 2.0 * rows * F * 3.0 * (F / ng), 4.0 * (3.0 * rows * F + 3.0 * F * (F / ng)));
+        continue;
+      }
       fx_gemm_desc d = gemm_desc(rows, F, 3 * F, conv_operand(dCat + h * F, 2 * F, F, dil, -1, q, false),
                                  op_rows(saved + (h == 0 ? L.wb1 : L.wb2) + (long long)i * 3 * F * F, 3 * F), dFn, F);
       if (h == 0) {
@@ -1282,7 +1351,12 @@ int fx_mstcn2_bwd(const fx_mstcn2_params* p, const fx_mstcn2_grads* g, const flo
         d.workspace = ws + L.bsl;
         FX_TRY(launch_gemm(d, sd));
       }
-      for (int h = 0; h < 2; ++h) {
+      for (int h = 0; h < 2 && ng > 1; ++h)   // grouped: one launch per conv and layer of this batch
+        for (int il = i0; il < i0 + nb; ++il)
+          FX_TRY(launch_gconv_dw(ws + L.dcat + 2 * il * L.rowsF + h * F, 2 * F, saved + L.f + il * L.rowsF, F, rows, T,
+                                 q.nvid, q.off, F, ng, mstcn2_dil(p, h == 0 ? NL - 1 - il : il),
+                                 (h == 0 ? g->w_d1 : g->w_d2)[il], (h == 0 ? g->b_d1 : g->b_d2)[il], ws + L.bsl, sd));
+      for (int h = 0; h < 2 && ng == 1; ++h) {
         // dilated conv h: dW_i += dC_h,i^T taps(f_i), db_i += colsum(dC_h,i); conv_d2's dilation grows with
         // the layer (batch b = layer i0 + b), conv_d1's shrinks: its batch b is layer NL-1-b (negative strides)
         const int il = (h == 0 && uni) ? NL - 1 : i0;
@@ -1326,6 +1400,53 @@ int fx_mstcn2_bwd(const fx_mstcn2_params* p, const fx_mstcn2_grads* g, const flo
     FX_CHECK_HIP(hipEventRecord(ss->join, sd));
     FX_CHECK_HIP(hipStreamWaitEvent(s, ss->join, 0));
   }
+  return FX_OK;
+}
+
+// ---------------------------------------------------------------- grouped dilated conv, one layer
+// workspace: [forward image | dX image | weight-gradient partials]
+long long fx_conv3g_workspace_floats(int rows, int F, int ngroup) {
+  if (F < 1 || ngroup < 0 || F % std::max(ngroup, 1) != 0) return 0;
+  return 2 * al64(gconv_packed_floats(F, ngroup)) + gconv_dw_ws_floats(rows, F, ngroup);
+}
+
+int fx_conv3g_fwd(const float* x, long long ldx, int rows, int T, int nvid, const int* seq_off, int F, int ngroup,
+                  int dil, const float* w, const float* b, int relu, float* y, long long ldy, float* workspace,
+                  void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  FX_TRY(gconv_check(F, ngroup, "fx_conv3g_fwd"));
+  FX_REQUIRE(x && w && y && workspace && rows >= 0 && dil >= 1, "fx_conv3g_fwd: bad arguments");
+  const int ng = std::max(ngroup, 1);
+  float* wf = workspace;
+  float* wb = wf + al64(gconv_packed_floats(F, ng));
+  const GPackJob job{w, wf, wb, nullptr, nullptr};
+  FX_TRY(launch_gconv_pack(&job, 1, F, ng, s));
+  prof_begin(0, s);
+  const int st = launch_gconv(x, ldx, rows, T, nvid, seq_off, F, ng, dil, 1, wf, b, relu, nullptr, 0, 0, y, ldy, s);
+  prof_end(0, s, 2.0 * rows * F * 3.0 * (F / ng), 4.0 * (2.0 * rows * F + 3.0 * F * (F / ng)));
+  return st;
+}
+
+int fx_conv3g_bwd(const float* x, long long ldx, int rows, int T, int nvid, const int* seq_off, int F, int ngroup,
+                  int dil, const float* w, const float* dy, long long lddy, float* dx, long long lddx, float* dw,
+                  float* db, float* workspace, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  FX_TRY(gconv_check(F, ngroup, "fx_conv3g_bwd"));
+  FX_REQUIRE(x && w && dy && workspace && rows >= 0 && dil >= 1, "fx_conv3g_bwd: bad arguments");
+  const int ng = std::max(ngroup, 1);
+  float* wf = workspace;
+  float* wb = wf + al64(gconv_packed_floats(F, ng));
+  float* part = wb + al64(gconv_packed_floats(F, ng));
+  if (dx) {
+    const GPackJob job{w, wf, wb, nullptr, nullptr};
+    FX_TRY(launch_gconv_pack(&job, 1, F, ng, s));
+    prof_begin(0, s);
+    const int st = launch_gconv(dy, lddy, rows, T, nvid, seq_off, F, ng, dil, -1, wb, nullptr, 0, nullptr, 0, 0, dx,
+                                lddx, s);
+    prof_end(0, s, 2.0 * rows * F * 3.0 * (F / ng), 4.0 * (2.0 * rows * F + 3.0 * F * (F / ng)));
+    FX_TRY(st);
+  }
+  if (dw || db) FX_TRY(launch_gconv_dw(dy, lddy, x, ldx, rows, T, nvid, seq_off, F, ng, dil, dw, db, part, s));
   return FX_OK;
 }
 

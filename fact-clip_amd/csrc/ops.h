@@ -188,4 +188,30 @@ int launch_frl(const float* x, long long ldx, int M, int T, int dil, int dir, co
                unsigned long long drop_seed, hipStream_t s, float vdrop_p = 0.f, unsigned long long vdrop_seed = 0,
                float* out3 = nullptr, long long ldo3 = 0);
 
+// ---- grouped dilated Conv1d(k = 3) (conv_grouped.hip): nn.Conv1d(F, F, 3, groups = ngroup), cg = F / ngroup ----
+// Videos: nvid of T rows (rows = T * nvid) or the ragged host row offsets seq_off (nvid + 1, <= 16 videos);
+// a shifted row outside its video reads as zero.  Always on the f32 MFMA, whatever the precision mode.
+int gconv_check(int F, int ngroup, const char* who);   // ngroup >= 0 and F % max(ngroup, 1) == 0, else FX_ERR_SHAPE
+long long gconv_packed_floats(int F, int ngroup);      // 3 F cg: one packed image
+// (F, cg, 3) -> wf [q][tap][n][c] (forward) and wb [q][tap][c][n] (input gradient); optionally a 1x1 weight
+// wpw (F, F) -> wpt transposed
+struct GPackJob {
+  const float* w;
+  float* wf;
+  float* wb;
+  const float* wpw;
+  float* wpt;
+};
+int launch_gconv_pack(const GPackJob* jobs, int n, int F, int ngroup, hipStream_t s);
+// y (+)= act(conv(x; wp) + bias) (+ resid): dir = 1 over the wf image is the forward, dir = -1 over wb the input
+// gradient; bias / resid nullable
+int launch_gconv(const float* x, long long ldx, int rows, int T, int nvid, const int* seq_off, int F, int ngroup,
+                 int dil, int dir, const float* wp, const float* bias, int relu, const float* resid, long long ldr,
+                 int accumulate, float* y, long long ldy, hipStream_t s);
+// dw (F, cg, 3) += dz^T taps(x), db (F) += colsum(dz) (either nullable): split-K partials in ws
+// (gconv_dw_ws_floats), reduced in split order -- deterministic, no atomics
+long long gconv_dw_ws_floats(int rows, int F, int ngroup);
+int launch_gconv_dw(const float* dz, long long lddz, const float* x, long long ldx, int rows, int T, int nvid,
+                    const int* seq_off, int F, int ngroup, int dil, float* dw, float* db, float* ws, hipStream_t s);
+
 }  // namespace fx

@@ -693,7 +693,7 @@ class MSTCNFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, meta, *params):
         lib = nx.load()
-        T, nvid, cin, F, cout, nl, ln, in_map, d0, dfac, drop_p, seed, seq_off = meta
+        T, nvid, cin, F, cout, nl, ln, in_map, d0, dfac, drop_p, seed, seq_off, ngroup = meta
         w_in, b_in, layers, w_out, b_out = MSTCNFn._unpack(meta, params)
         keep = []
         prm = nx.MstcnParams()
@@ -711,6 +711,7 @@ class MSTCNFn(torch.autograd.Function):
         prm.w_out, prm.b_out = nx.ptr(w_out), nx.ptr(b_out)
         prm.dropout, prm.seed = float(drop_p), int(seed)
         prm.fused_layers = int(MSTCN_FUSED_LAYERS)
+        prm.ngroup = int(ngroup)     # grouped dilated convs (f_ngp); 1: dense
         rows = x.shape[0]
         dev = x.device
         y = _empty(rows, cout, device=dev)
@@ -769,7 +770,7 @@ def mstcn(mod, x, T, nvid=1, seq_off=None):
     p = float(mod.dropout_rate) if (mod.training and mod.dropout_rate) else 0.0
     meta = (T, nvid, x2.shape[1], mod.hid_dim, mod.out_dim, mod.num_layers, bool(ln), bool(mod.in_map),
             mod.dilation0, mod.dilation_factor, p, dropout_seed() if p > 0 else 0,
-            None if seq_off is None else tuple(int(v) for v in seq_off))
+            None if seq_off is None else tuple(int(v) for v in seq_off), int(getattr(mod, "ngroup", 1)))
     return MSTCNFn.apply(x2, meta, *params)
 
 
@@ -793,11 +794,12 @@ class MSTCN2Fn(torch.autograd.Function):
 
     @staticmethod
     def _prm(meta, params, keep, cls, grads=False):
-        T, nvid, cin, F, cout, nl, in_map, dfac, drop_p, seed, seq_off = meta
+        T, nvid, cin, F, cout, nl, in_map, dfac, drop_p, seed, seq_off, ngroup = meta
         w_in, b_in, groups, w_out, b_out = MSTCN2Fn._unpack(meta, params)
         prm = cls()
         if not grads:
             prm.cin, prm.F, prm.cout, prm.num_layers, prm.in_map, prm.dil_factor = cin, F, cout, nl, int(in_map), dfac
+            prm.ngroup = int(ngroup)     # grouped dilated convs (f_ngp); 1: dense
             prm.dropout, prm.seed = float(drop_p), int(seed)
             if seq_off is not None:
                 so = nx.int_array(seq_off)
@@ -861,7 +863,7 @@ def mstcn2(mod, x, T, nvid=1, drop_p=0.0, seq_off=None):
     params += [mod.conv_out.weight, mod.conv_out.bias]
     meta = (T, nvid, x2.shape[1], mod.conv_out.weight.shape[1], mod.conv_out.weight.shape[0], L, bool(mod.in_map),
             int(mod.dilation_factor), float(drop_p), dropout_seed() if drop_p > 0 else 0,
-            None if seq_off is None else tuple(int(v) for v in seq_off))
+            None if seq_off is None else tuple(int(v) for v in seq_off), int(getattr(mod, "ngroup", 1)))
     return MSTCN2Fn.apply(x2, meta, *params)
 
 
@@ -930,12 +932,24 @@ def matmul_tn(a, b):
 
 
 class Conv3Fn(torch.autograd.Function):
-    """Conv1d(k=3, dilation d, padding d) on (T*nvid, C) rows as an implicit GEMM (basic.py:138, 237-245)."""
+    """Conv1d(k=3, dilation d, padding d) on (T*nvid, C) rows as an implicit GEMM (basic.py:138, 237-245);
+    groups = x.shape[1] // w.shape[1] > 1 (w (C, C / groups, 3)) runs the grouped conv kernels."""
 
     @staticmethod
     def forward(ctx, x, w, b, dil, T):
         rows, cin = x.shape
         cout = w.shape[0]
+        ctx.ngroup = ngroup = cin // w.shape[1]
+        if ngroup > 1:      # nn.Conv1d(groups=): w (F, F / ngroup, 3), the grouped kernels (fx_conv3g_*)
+            lib = nx.load()
+            x, w = x.contiguous(), w.contiguous()
+            y = _empty(rows, cout, device=x.device)
+            ws = _ws(lib.fx_conv3g_workspace_floats(rows, cout, ngroup), x.device)
+            _check(lib.fx_conv3g_fwd(nx.ptr(x), nx.ld(x), rows, T, rows // T, None, cout, ngroup, dil, nx.ptr(w),
+                                     nx.ptr(b), 0, nx.ptr(y), cout, nx.ptr(ws), nx.stream()), "fx_conv3g_fwd")
+            ctx.dil, ctx.T = dil, T
+            ctx.save_for_backward(x, w, b)
+            return y
         wf = w.permute(0, 2, 1).reshape(cout, 3 * cin).contiguous()       # [n][tap][c]
         y = _empty(rows, cout, device=x.device)
         gemm(rows, cout, 3 * cin, _conv_operand(x, cin, dil, 1, T, False), _rows_operand(wf), y, cout, bias=b)
@@ -952,6 +966,16 @@ class Conv3Fn(torch.autograd.Function):
         cout = w.shape[0]
         dev = x.device
         dx = None
+        if ctx.ngroup > 1:
+            lib = nx.load()
+            dx = _empty(rows, cin, device=dev) if nd[0] else None
+            dwb, dw_ret = grad_target(w, nd[1])
+            dbb, db_ret = grad_target(b, nd[2])
+            ws = _ws(lib.fx_conv3g_workspace_floats(rows, cout, ctx.ngroup), dev)
+            _check(lib.fx_conv3g_bwd(nx.ptr(x), nx.ld(x), rows, ctx.T, rows // ctx.T, None, cout, ctx.ngroup, ctx.dil,
+                                     nx.ptr(w), nx.ptr(dy), cout, nx.ptr(dx), cin, nx.ptr(dwb), nx.ptr(dbb),
+                                     nx.ptr(ws), nx.stream()), "fx_conv3g_bwd")
+            return dx, dw_ret, db_ret, None, None
         if nd[0]:
             wb = w.permute(1, 2, 0).reshape(cin, 3 * cout).contiguous()   # [c][tap][n]
             dx = _empty(rows, cin, device=dev)

@@ -110,10 +110,9 @@ class DilatedResidualLayer(nn.Module):
 
     def __init__(self, dilation, nchannels, dropout=0.5, layernorm=True, layernorm_eps=1e-5, ngroup=1):
         super().__init__()
-        if ngroup != 1:
-            raise NotImplementedError("grouped dilated conv (f_ngp != 1) is not implemented")
         self.dilation = dilation
         self.nchannels = nchannels
+        self.ngroup = ngroup
         self.dropout_rate = dropout
         self.conv_dilated = nn.Conv1d(nchannels, nchannels, 3, padding=dilation, dilation=dilation, groups=ngroup)
         self.conv_1x1 = nn.Conv1d(nchannels, nchannels, 1)
@@ -157,6 +156,7 @@ class MSTCN(nn.Module):
         self.dropout_rate = dropout
         self.dilation_factor = dilation_factor
         self.dilation0 = 1
+        self.ngroup = ngroup
         self.string = (f"MSTCN(h:{in_dim}->{hid_dim}x{num_layers}->{out_dim}, d={dilation_factor}, ng={ngroup}, "
                        f"dropout={dropout}, in_map={in_map})")
 
@@ -178,9 +178,8 @@ class MSTCN2(nn.Module):
                  in_map=True):
         super().__init__()
         assert ln is False or ln == 0
-        if ngroup != 1:
-            raise NotImplementedError("grouped dilated conv (f_ngp != 1) is not implemented")
         self.num_layers = num_layers
+        self.ngroup = ngroup
         self.in_map = in_map
         if in_map:
             self.conv_1x1_in = nn.Conv1d(dim, num_f_maps, 1)

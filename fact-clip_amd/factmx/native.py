@@ -12,7 +12,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FACTMX_LIB", os.path.join(_HERE, "_lib", "libfactmx.so"))
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 P = ctypes.c_void_p
 I = ctypes.c_int
@@ -46,14 +46,14 @@ class MstcnParams(ctypes.Structure):
     _fields_ = [("cin", I), ("F", I), ("cout", I), ("num_layers", I), ("layernorm", I), ("in_map", I),
                 ("dil0", I), ("dil_factor", I), ("w_in", P), ("b_in", P), ("w_dil", P), ("b_dil", P), ("w_pw", P), ("b_pw", P),
                 ("ln_w", P), ("ln_b", P), ("w_out", P), ("b_out", P), ("dropout", F), ("seed", U),
-                ("side_defer", I), ("seq_off", P), ("fused_layers", I)]
+                ("side_defer", I), ("seq_off", P), ("fused_layers", I), ("ngroup", I)]
 
 
 class Mstcn2Params(ctypes.Structure):
     _fields_ = [("cin", I), ("F", I), ("cout", I), ("num_layers", I), ("in_map", I), ("dil_factor", I),
                 ("w_in", P), ("b_in", P), ("w_d1", P), ("b_d1", P), ("w_d2", P), ("b_d2", P), ("w_fu", P),
                 ("b_fu", P), ("w_out", P), ("b_out", P), ("dropout", F), ("seed", U), ("side_defer", I),
-                ("seq_off", P)]
+                ("seq_off", P), ("ngroup", I)]
 
 
 class Mstcn2Grads(ctypes.Structure):
@@ -141,6 +141,9 @@ SIGNATURES = {
     "fx_mstcn2_workspace_floats": (L, [ctypes.POINTER(Mstcn2Params), I]),
     "fx_mstcn2_fwd": (I, [ctypes.POINTER(Mstcn2Params), P, L, I, I, P, L, P, P, P]),
     "fx_mstcn2_bwd": (I, [ctypes.POINTER(Mstcn2Params), ctypes.POINTER(Mstcn2Grads), P, L, I, I, P, L, P, L, P, P, P]),
+    "fx_conv3g_workspace_floats": (L, [I, I, I]),
+    "fx_conv3g_fwd": (I, [P, L, I, I, I, P, I, I, I, P, P, I, P, L, P, P]),
+    "fx_conv3g_bwd": (I, [P, L, I, I, I, P, I, I, I, P, P, L, P, L, P, P, P, P]),
     "fx_layernorm_fwd": (I, [P, L, P, L, P, P, F, I, I, I, P, L, P, L, P, P]),
     "fx_layernorm_bwd_workspace_floats": (L, [I, I]),
     "fx_layernorm_bwd": (I, [P, L, P, L, P, L, P, P, I, I, I, P, L, P, P, P, P]),

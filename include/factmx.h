@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define FX_ABI_VERSION 20
+#define FX_ABI_VERSION 21
 
 enum {
   FX_OK = 0,
@@ -287,7 +287,7 @@ int fx_decoder_bwd(const fx_decoder_params* p, const fx_decoder_grads* g, const 
  * (basic.py:154-171) unrolled over num_layers, dilation 2^i, eval-mode dropout.
  *   x (T*nvid, cin) -> y (T*nvid, cout);   hidden width F.
  *   w_in/b_in: Conv1d(cin->F, k=1) weights (nullable when in_map == 0, cin == F)
- *   w_dil[i] (F,F,3), b_dil[i], w_pw[i] (F,F,1), b_pw[i]; ln_w/ln_b[i] (nullable)
+ *   w_dil[i] (F,F/ngroup,3), b_dil[i], w_pw[i] (F,F,1), b_pw[i]; ln_w/ln_b[i] (nullable)
  *   w_out (cout,F,1), b_out.
  *   saved (caller-owned, fx_mstcn_saved_floats): activations kept for backward.
  * ---------------------------------------------------------------------- */
@@ -316,6 +316,11 @@ typedef struct fx_mstcn_params {
                                  applies (tests); 0: the two GEMMs per layer.  The backward's fused dX
                                  chain needs the deferred weight gradients (uniformly strided gradient
                                  buffers) when dropout is on: it keeps the masked 1x1 gradient dB_i */
+  int ngroup;                 /* groups of every layer's dilated conv (nn.Conv1d groups=, the reference's
+                                 f_ngp); 0 and 1: dense.  Must divide F.  > 1: w_dil[i] is (F, F/ngroup, 3)
+                                 and the dilated convs run the grouped kernels (fx_conv3g_*: f32 MFMA in
+                                 every precision mode); the fused layer and the batched weight-gradient
+                                 schedule are off, the 1x1, LayerNorm and in/out maps are unchanged */
 } fx_mstcn_params;
 
 typedef struct fx_mstcn_grads {
@@ -344,7 +349,7 @@ int fx_mstcn_bwd(const fx_mstcn_params* p, const fx_mstcn_grads* g, const float*
  *   f' = f + dropout_i(relu(W_fu,i . cat[conv_d1,i(f), conv_d2,i(f)] + b_fu,i)),
  * conv_d1,i dilation dil_factor^(L-1-i), conv_d2,i dilation dil_factor^i, no dropout on the last
  * layer, then conv_out) for nvid stacked videos of T rows (zero padding at every video's ends).
- * Weight shapes as the reference's Conv1d (w_d*: (F, F, 3), w_fu: (F, 2F)); ngroup 1, no LN.
+ * Weight shapes as the reference's Conv1d (w_d*: (F, F/ngroup, 3), w_fu: (F, 2F)); no LN.
  * Gradients ACCUMULATE; the weight-gradient GEMMs of all layers run after the input-gradient chain
  * as batched launches on the side stream (per layer when the gradient buffers are not uniformly
  * strided).  side_defer as fx_mstcn_params.
@@ -360,6 +365,8 @@ typedef struct fx_mstcn2_params {
   unsigned long long seed;
   int side_defer;
   const int* seq_off;         /* ragged videos, as fx_mstcn_params.seq_off */
+  int ngroup;                 /* groups of both dilated convs of every layer, as fx_mstcn_params.ngroup
+                                 (0 and 1: dense); the fusion 1x1 stays dense */
 } fx_mstcn2_params;
 
 typedef struct fx_mstcn2_grads {
@@ -377,6 +384,27 @@ int fx_mstcn2_fwd(const fx_mstcn2_params* p, const float* x, long long ldx, int 
 int fx_mstcn2_bwd(const fx_mstcn2_params* p, const fx_mstcn2_grads* g, const float* x, long long ldx,
                   int T, int nvid, const float* dy, long long lddy, float* dx, long long lddx,
                   const float* saved, float* workspace, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Grouped dilated Conv1d(k=3, dilation dil, padding dil, groups=ngroup) on (rows, F) frame rows: one
+ * layer (DilatedResidualLayer.conv_dilated with f_ngp > 1, basic.py:138).  cg = F / ngroup; w is
+ * nn.Conv1d's (F, cg, 3), b (F) nullable.  Videos: nvid of T rows (rows = T * nvid), or the ragged host
+ * row offsets seq_off (nvid + 1, nvid <= 16; T ignored); a tap outside its video reads zero.
+ *   fwd: y = conv(x) + b, ReLU when relu != 0.
+ *   bwd: dy is the gradient at the conv's output (the caller applies a ReLU mask first);
+ *        dx = conv^T(dy) written, dw (F, cg, 3) and db (F) ACCUMULATED; each nullable.  The weight
+ *        gradient's split-K partials are reduced in a fixed order: two runs give the same bits.
+ * workspace: fx_conv3g_workspace_floats(rows, F, ngroup) floats (packed weights + partials), 16-byte
+ * aligned.  ngroup must be >= 0 and divide F (0 and 1: one group), else FX_ERR_SHAPE.  The products
+ * always run on v_mfma_f32_32x32x2_f32, whatever the stream's precision mode.
+ * ---------------------------------------------------------------------- */
+long long fx_conv3g_workspace_floats(int rows, int F, int ngroup);
+int fx_conv3g_fwd(const float* x, long long ldx, int rows, int T, int nvid, const int* seq_off, int F,
+                  int ngroup, int dil, const float* w, const float* b, int relu, float* y, long long ldy,
+                  float* workspace, void* stream);
+int fx_conv3g_bwd(const float* x, long long ldx, int rows, int T, int nvid, const int* seq_off, int F,
+                  int ngroup, int dil, const float* w, const float* dy, long long lddy, float* dx,
+                  long long lddx, float* dw, float* db, float* workspace, void* stream);
 
 /* ------------------------------------------------------------------------
  * Row-wise LayerNorm with fused residual (post-norm residual blocks,
@@ -696,8 +724,9 @@ int fx_eval_pred(const fx_video_attn* vids_host, const fx_video_attn* vids_dev, 
  * receives): fx_set_stream_precision(stream, prec) applies to the GEMMs later
  * enqueued on that stream; streams never set follow the library default
  * (fx_set_default_precision, initially FX_PREC_F32).  Weight-gradient GEMMs
- * (column-major A) and the small-tile / direct kernels always multiply on the
- * f32 MFMA.  FX_PREC_F32: every product on v_mfma_f32_32x32x2_f32.  FX_PREC_BF16: the
+ * (column-major A), the small-tile / direct kernels and the grouped dilated
+ * convs (ngroup > 1, fx_conv3g_*) always multiply on the f32 MFMA.
+ * FX_PREC_F32: every product on v_mfma_f32_32x32x2_f32.  FX_PREC_BF16: the
  * frame-level GEMMs with row-major operands (forward and input-gradient
  * products of the MS-TCN convs, in/out maps, projections) round their
  * operands to bf16 on the way into LDS and multiply on
