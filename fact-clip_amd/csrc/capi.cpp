@@ -1757,7 +1757,7 @@ long long x2y_split_ws1(int Nx, int xdim, int Ny, int ydim, int Hd, int outdim) 
 }
 long long x2y_split_ws(const VidRows& v, int xdim, int ydim, int Hd, int outdim) {
   long long sp = x2y_split_ws1(v.x[v.n], xdim, v.y[v.n], ydim, Hd, outdim);
-  if (Hd % 32 == 0) sp = std::max(sp, x2y_a2f_dw_ws_floats(v.n, Hd));   // (the a2f dW kernel's partials)
+  if (Hd % 32 == 0) sp = std::max(sp, x2y_a2f_dw_ws_floats(v.n, Hd, v.x.data()));   // (the a2f dW kernel's partials)
   for (int i = 0; i < v.n; ++i)
     sp = std::max(sp, x2y_split_ws1(v.x[i + 1] - v.x[i], xdim, v.y[i + 1] - v.y[i], ydim, Hd, outdim));
   return sp;
@@ -1797,7 +1797,19 @@ long long fx_x2y_workspace_floats(int Nx, int xdim, int Ny, int ydim, int Hd, in
                                   const int* x_off, const int* y_off) {
   const VidRows v = vid_rows(Nx, Ny, nvid, x_off, y_off);
   return x2y_ws_nocatd(Nx, xdim, Ny, ydim, Hd, outdim, v) + al64((long long)Ny * (ydim + Hd)) +
-         x2y_side_ws(Nx, xdim, Ny, ydim, Hd, outdim) + x2y_f2a_ws_floats(v.n, v.x.data(), Hd);
+         x2y_side_ws(Nx, xdim, Ny, ydim, Hd, outdim) + x2y_f2a_ws_floats(v.n, v.x.data(), v.y.data(), Hd);
+}
+
+int fx_x2y_core(int Hd, int nvid, const int* x_off, const int* y_off, int Nx, int Ny) {
+  if (Hd <= 0 || Nx < 0 || Ny < 0) return 0;
+  const VidRows v = vid_rows(Nx, Ny, nvid, x_off, y_off);
+  switch (x2y_core_pick(v.n, v.x.data(), v.y.data(), Hd)) {
+    case FX_X2Y_CORE_A2F:
+    case FX_X2Y_CORE_A2F_WIDE: return 1;
+    case FX_X2Y_CORE_F2A:
+    case FX_X2Y_CORE_F2A_WIDE: return 2;
+    default: return 0;
+  }
 }
 
 // catd = dropout(cat[Y, feat]) (basic.py:382), mask index r (ydim + Hd) + c
@@ -1848,7 +1860,7 @@ int fx_x2y_fwd(const float* X, long long ldx, int Nx, int xdim, const float* Xpo
   prof_end(10, s, 2.0 * Hd * (2.0 * Nx * xdim + (double)Ny * ydim),
            4.0 * (2.0 * Nx * xdim + (double)Ny * ydim + Hd * (2.0 * xdim + ydim) + Hd * (2.0 * Nx + Ny)), 3);
   const float scale = 1.0f / std::sqrt((float)Hd);
-  // a short key side (the a2f map: <= 64 action tokens per video): the whole core in one launch
+  // a short key side (the a2f map: <= 320 action tokens per video): the whole core in one launch
   const bool al16 =
       ((reinterpret_cast<uintptr_t>(yq) | reinterpret_cast<uintptr_t>(xk) | reinterpret_cast<uintptr_t>(xv)) & 15) == 0;
   // algorithmic bytes of the attention core (bench roofline_attention): the query / key / value rows, the
@@ -1857,11 +1869,12 @@ int fx_x2y_fwd(const float* X, long long ldx, int Nx, int xdim, const float* Xpo
   const double core_bytes = 4.0 * ((double)Ny * Hd + 2.0 * Nx * Hd + 2.0 * na + (double)Ny * Hd);
   // fx_prof kinds 3 / 5 for frame-level calls, 11 / 13 for segment-level ones (bench.py reports them apart)
   const int kseg = std::max(Nx, Ny) >= 1024 ? 0 : 8;
-  if (knobs().x2y_fused && x2y_a2f_fusable(V.n, V.x.data(), Hd) && al16) {
+  const int core = knobs().x2y_fused && al16 ? x2y_core_pick(V.n, V.x.data(), V.y.data(), Hd) : FX_X2Y_CORE_NONE;
+  if (core == FX_X2Y_CORE_A2F || core == FX_X2Y_CORE_A2F_WIDE) {
     prof_begin(3 + kseg, s);
     FX_TRY(launch_x2y_a2f_fwd(yq, xk, xv, Hd, scale, V.n, V.y.data(), V.x.data(), V.a.data(), logit, attn, feat, s));
     prof_end(3 + kseg, s, 4.0 * na * Hd, core_bytes);
-  } else if (knobs().x2y_fused && x2y_f2a_fusable(V.n, V.x.data(), V.y.data(), Hd) && al16) {
+  } else if (core == FX_X2Y_CORE_F2A || core == FX_X2Y_CORE_F2A_WIDE) {
     // the f2a map (frames -> tokens): per-chunk partials after every other region of the workspace
     float* f2a_ws = workspace + x2y_ws_nocatd(Nx, xdim, Ny, ydim, Hd, outdim, V) + al64((long long)Ny * (ydim + Hd)) +
                     x2y_side_ws(Nx, xdim, Ny, ydim, Hd, outdim);
@@ -1962,7 +1975,9 @@ int fx_x2y_bwd(const float* X, long long ldx, int Nx, int xdim, int xpos_cols, c
   // the forward's (X2YLayout offsets Nx*xdim + Ny*ydim (+k*Nx*Hd) need not be multiples of 4 floats)
   const bool al16 = ((reinterpret_cast<uintptr_t>(xk) | reinterpret_cast<uintptr_t>(xv) |
                       reinterpret_cast<uintptr_t>(yq) | reinterpret_cast<uintptr_t>(dcat + ydim)) & 15) == 0;
-  const bool fused = knobs().x2y_fused && x2y_a2f_fusable(V.n, V.x.data(), Hd) && (cw & 3) == 0 && al16;
+  const int core = knobs().x2y_fused && (cw & 3) == 0 && al16 ? x2y_core_pick(V.n, V.x.data(), V.y.data(), Hd)
+                                                                : FX_X2Y_CORE_NONE;
+  const bool fused = core == FX_X2Y_CORE_A2F || core == FX_X2Y_CORE_A2F_WIDE;
   // algorithmic bytes of the backward core: dfeat, xv, xk, yq, attn (+ dattn / dlogit in), dlogit, dxv,
   // dxk, dyq out
   const double na = (double)V.a[V.n];
@@ -1970,9 +1985,10 @@ int fx_x2y_bwd(const float* X, long long ldx, int Nx, int xdim, int xpos_cols, c
   // the fused f2a core (bracketed as fx_prof kind 6 only when it runs: the per-video GEMM fallback below
   // is not the kernel whose algorithmic bytes kind 6 reports)
   const int f2a_mode = knobs().x2y_f2a_bwd;
-  const bool f2a_fused = !fused && knobs().x2y_fused &&
-                         (f2a_mode == 1 || (f2a_mode == 2 && x2y_f2a_chunks(V.n, V.x.data()) >= 64)) &&
-                         x2y_f2a_fusable(V.n, V.x.data(), V.y.data(), Hd) && (cw & 3) == 0 && al16;
+  // (the wide f2a backward measured slower than the grouped GEMMs at every token count: FX_X2Y_F2A_BWD=1 only)
+  const bool f2a_fused = (core == FX_X2Y_CORE_F2A || core == FX_X2Y_CORE_F2A_WIDE) &&
+                         (f2a_mode == 1 || (f2a_mode == 2 && core == FX_X2Y_CORE_F2A &&
+                                            x2y_f2a_chunks(V.n, V.x.data()) >= 64));
   const int kseg = std::max(Nx, Ny) >= 1024 ? 0 : 8;   // (fx_prof: frame-level 4 / 6, segment-level 12 / 14)
   if (fused) prof_begin(4 + kseg, s);
   else if (f2a_fused) prof_begin(6 + kseg, s);

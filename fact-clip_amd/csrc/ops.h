@@ -62,18 +62,27 @@ int launch_gru_bwd(const float* dout, long long lddo, const float* relu_y, long 
                    int Hh, const float* const whh[2], const float* saved, float* dgi, long long lddgi, float* dgh,
                    float* sync_ws, unsigned* status, int spin_max, hipStream_t s);
 
-// X2Y attention core with <= 64 keys per video (x2y_core.hip): logit, attn, feat in one launch;
-// yoff / xoff: (nvid + 1) host row offsets, aoff: attention block offsets (ny_v * nx_v row-major each)
+// X2Y attention cores (x2y_core.hip).  Token rows per video (keys of the a2f core, queries of the f2a core):
+// <= 64 take the original kernels, 65 .. FX_X2Y_MAXTOK their wide variants (the launchers choose by the call's
+// widest video); yoff / xoff: (nvid + 1) host row offsets, aoff: attention block offsets (ny_v * nx_v
+// row-major each)
+constexpr int FX_X2Y_MAXTOK = 320;
+// which core a call takes -- the ONE decision behind fx_x2y_fwd, fx_x2y_bwd, fx_x2y_workspace_floats and
+// fx_x2y_core (alignment and the FX_X2Y_* knobs aside)
+enum { FX_X2Y_CORE_NONE = 0, FX_X2Y_CORE_A2F = 1, FX_X2Y_CORE_F2A = 2, FX_X2Y_CORE_A2F_WIDE = 3, FX_X2Y_CORE_F2A_WIDE = 4 };
+int x2y_core_pick(int nvid, const int* xoff, const int* yoff, int Hd);
+// short key side (a2f: <= 320 keys per video): logit, attn, feat in one launch;
+// x2y_a2f_fusable / x2y_f2a_fusable: the <= 64-row conditions
 bool x2y_a2f_fusable(int nvid, const int* xoff, int Hd);
 int launch_x2y_a2f_fwd(const float* yq, const float* xk, const float* xv, int Hd, float scale, int nvid,
                        const int* yoff, const int* xoff, const long long* aoff, float* logit, float* attn,
                        float* feat, hipStream_t s);
-// long key side (f2a: <= 64 queries per video over up to T keys): chunk kernel + ordered merge; ws holds
-// x2y_f2a_ws_floats(...) floats of per-chunk partials
+// long key side (f2a: <= 320 queries per video over up to T keys): chunk kernel + ordered merge; ws holds
+// x2y_f2a_ws_floats(...) floats of per-chunk partials (slabs of 64 x the query blocks of the widest video)
 bool x2y_f2a_fusable(int nvid, const int* xoff, const int* yoff, int Hd);
 // 64-key chunks (= workgroups of the fused f2a backward passes) of a call
 long long x2y_f2a_chunks(int nvid, const int* xoff);
-long long x2y_f2a_ws_floats(int nvid, const int* xoff, int Hd);
+long long x2y_f2a_ws_floats(int nvid, const int* xoff, const int* yoff, int Hd);
 int launch_x2y_f2a_fwd(const float* yq, const float* xk, const float* xv, int Hd, float scale, int nvid,
                        const int* yoff, const int* xoff, const long long* aoff, float* logit, float* attn,
                        float* feat, float* ws, hipStream_t s);
@@ -87,8 +96,9 @@ int launch_x2y_f2a_bwd(const float* dfeat, long long ldf, const float* xv, const
 // backward, input-gradient side: dP = dfeat . xv^T (+ dattn), dlogit = attn (dP - rowsum(attn dP)) (+ dlogit_in),
 // dyq = scale dlogit . xk;  dfeat rows ld ldf (16-B aligned)
 // the a2f backward's weight-side products dxv = attn^T dfeat, dxk = scale dlogit^T yq in one launch
-// (x2y_a2f_dw_kernel); ws: x2y_a2f_dw_ws_floats(nvid, Hd) floats
-long long x2y_a2f_dw_ws_floats(int nvid, int Hd);
+// (x2y_a2f_dw_kernel; <= 320 keys per video, 64-key blocks of the output as a grid dimension);
+// ws: x2y_a2f_dw_ws_floats(nvid, Hd, xoff) floats
+long long x2y_a2f_dw_ws_floats(int nvid, int Hd, const int* xoff);
 bool x2y_a2f_dw_ok(int nvid, const int* yoff);   // every video within the kernel's row chunks
 int launch_x2y_a2f_dw(const float* attn, const float* dl, const float* dfeat, long long ldf, const float* yq, int Hd,
                       float scale, int nvid, const int* yoff, const int* xoff, const long long* aoff, float* dxv,

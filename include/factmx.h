@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define FX_ABI_VERSION 21
+#define FX_ABI_VERSION 22
 
 enum {
   FX_OK = 0,
@@ -172,6 +172,12 @@ int fx_linear_bwd(const float* dy, long long lddy, const float* x, long long ldx
 long long fx_x2y_saved_floats(int Nx, int xdim, int Ny, int ydim, int Hd);
 long long fx_x2y_workspace_floats(int Nx, int xdim, int Ny, int ydim, int Hd, int outdim, int nvid,
                                   const int* x_off, const int* y_off);
+/* which attention core fx_x2y_fwd / fx_x2y_bwd take for these row counts (alignment and knobs aside):
+ * 0 grouped GEMMs, 1 the short-key (a2f) core, 2 the long-key (f2a) core.  Host only: nothing is
+ * launched.  The cores take up to 320 action tokens per video (keys of the a2f core, queries of the
+ * f2a core; past 64 of them only in calls of at least 1024 X or Y rows -- smaller calls measured faster
+ * on the grouped GEMMs), Hd % 256 == 0, Hd <= 512, at most 16 videos and 1024 64-key chunks per video. */
+int fx_x2y_core(int Hd, int nvid, const int* x_off, const int* y_off, int Nx, int Ny);
 int fx_x2y_fwd(const float* X, long long ldx, int Nx, int xdim, const float* Xpos, long long ldxp,
                int xpos_cols, const float* Y, long long ldy, int Ny, int ydim, const float* Ypos,
                long long ldyp, int ypos_cols, const float* wk, const float* bk, const float* wv,
