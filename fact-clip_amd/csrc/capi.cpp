@@ -1542,6 +1542,37 @@ int fx_process_feature_bwd(const float* out, long long ldo, const float* dout, l
   return launch_pf_bwd(out, ldo, dout, lddo, dclogit, lddc, rows, cols, n, dx, lddx, (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------- verb / noun class heads (verbnoun.hip)
+int fx_process_feature2_fwd(const float* x, long long ldx, int rows, int cols, int n1, int n2, float* out,
+                            long long ldo, float* clogit, long long ldc, void* stream) {
+  return launch_pf2_fwd(x, ldx, rows, cols, n1, n2, out, ldo, clogit, ldc, (hipStream_t)stream);
+}
+
+int fx_process_feature2_bwd(const float* out, long long ldo, const float* dout, long long lddo, const float* dclogit,
+                            long long lddc, int rows, int cols, int n1, int n2, float* dx, long long lddx,
+                            void* stream) {
+  return launch_pf2_bwd(out, ldo, dout, lddo, dclogit, lddc, rows, cols, n1, n2, dx, lddx, (hipStream_t)stream);
+}
+
+int fx_vn_logp_fwd(const float* clogit, long long ldc, int rows, int n1, int n2, const int32_t* vids,
+                   const int32_t* nids, int A, int null, float* logp, long long ldl, float* lse, void* stream) {
+  return launch_vn_logp_fwd(clogit, ldc, rows, n1, n2, vids, nids, A, null, logp, ldl, lse, (hipStream_t)stream);
+}
+
+int fx_vn_logp_bwd(const float* clogit, long long ldc, const float* lse, const float* dlogp, long long ldg, int rows,
+                   int n1, int n2, int A, int null, const int32_t* voff, const int32_t* vlist, const int32_t* noff,
+                   const int32_t* nlist, float* dclogit, long long lddc, void* stream) {
+  return launch_vn_logp_bwd(clogit, ldc, lse, dlogp, ldg, rows, n1, n2, A, null, voff, vlist, noff, nlist, dclogit,
+                            lddc, (hipStream_t)stream);
+}
+
+int fx_segments_from_vn_probs(const float* x, long long ldx, int col0, int n1, int n2, const int32_t* vids,
+                              const int32_t* nids, int A, int T, int nvid, const int* row_off, int32_t* pred,
+                              int32_t* seg_id, int32_t* seg_start, int32_t* seg_end, int32_t* num_seg, void* stream) {
+  return launch_segments_vn(x, ldx, col0, n1, n2, vids, nids, A, T, nvid, row_off, pred, seg_id, seg_start, seg_end,
+                            num_seg, (hipStream_t)stream);
+}
+
 int fx_l2norm_fwd(const float* x, long long ldx, int rows, int cols, float* y, long long ldy, float* norm,
                   void* stream) {
   return launch_l2n_fwd(x, ldx, rows, cols, y, ldy, norm, (hipStream_t)stream);

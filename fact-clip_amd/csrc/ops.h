@@ -46,6 +46,24 @@ int launch_l2n_bwd(const float* y, long long ldy, const float* nrm, const float*
 int launch_segments(const float* x, long long ldx, int col0, int ncls, int T, int nvid, const int* row_off,
                     int32_t* pred, int32_t* seg_id, int32_t* seg_start, int32_t* seg_end, int32_t* num_seg,
                     hipStream_t s);
+// the two halves of launch_segments after its argmax, shared with the verb/noun argmax (verbnoun.hip):
+// the row-layout checks (*rows = total rows) and the per-video boundary scan of pred
+int segments_check_rows(int T, int nvid, const int* row_off, int* rows);
+int launch_boundary_scan(const int32_t* pred, int T, int nvid, const int* row_off, int32_t* seg_id,
+                         int32_t* seg_start, int32_t* seg_end, int32_t* num_seg, hipStream_t s);
+// verb / noun class heads (verbnoun.hip; blocks_SepVerbNoun.py)
+int launch_pf2_fwd(const float* x, long long ldx, int rows, int cols, int n1, int n2, float* out, long long ldo,
+                   float* clogit, long long ldc, hipStream_t s);
+int launch_pf2_bwd(const float* out, long long ldo, const float* dout, long long lddo, const float* dcl,
+                   long long lddc, int rows, int cols, int n1, int n2, float* dx, long long lddx, hipStream_t s);
+int launch_vn_logp_fwd(const float* clogit, long long ldc, int rows, int n1, int n2, const int32_t* vids,
+                       const int32_t* nids, int A, int null, float* logp, long long ldl, float* lse, hipStream_t s);
+int launch_vn_logp_bwd(const float* clogit, long long ldc, const float* lse, const float* dlogp, long long ldg,
+                       int rows, int n1, int n2, int A, int null, const int32_t* voff, const int32_t* vlist,
+                       const int32_t* noff, const int32_t* nlist, float* dclogit, long long lddc, hipStream_t s);
+int launch_segments_vn(const float* x, long long ldx, int col0, int n1, int n2, const int32_t* vids,
+                       const int32_t* nids, int A, int T, int nvid, const int* row_off, int32_t* pred,
+                       int32_t* seg_id, int32_t* seg_start, int32_t* seg_end, int32_t* num_seg, hipStream_t s);
 int launch_seg_globalize(int nvid, int T, const int* row_off, const int32_t* num_seg_host, const int32_t* seg_id,
                          const int32_t* st, const int32_t* en, int32_t* gseg_id, int32_t* gst, int32_t* gen,
                          hipStream_t s);

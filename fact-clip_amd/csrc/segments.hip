@@ -10,6 +10,7 @@
 #include <algorithm>
 
 #include "fx_common.h"
+#include "ops.h"
 
 namespace fx {
 namespace {
@@ -203,10 +204,22 @@ int launch_seg_globalize(int nvid, int T, const int* row_off, const int32_t* num
 int launch_segments(const float* x, long long ldx, int col0, int ncls, int T, int nvid, const int* row_off,
                     int32_t* pred, int32_t* seg_id, int32_t* seg_start, int32_t* seg_end, int32_t* num_seg,
                     hipStream_t s) {
-  FX_REQUIRE(ncls > 0 && nvid >= 1 && (row_off || T > 0), "segments: need T > 0 (or row offsets) and ncls > 0");
-  const int rows = row_of(T, row_off, nvid);
-  for (int v = 0; v < nvid; ++v) FX_REQUIRE(row_of(T, row_off, v + 1) > row_of(T, row_off, v), "segments: empty video");
+  FX_REQUIRE(ncls > 0, "segments: need T > 0 (or row offsets) and ncls > 0");
+  int rows = 0;
+  FX_TRY(segments_check_rows(T, nvid, row_off, &rows));
   fx_launch(argmax_rows_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, s, x, ldx, col0, ncls, rows, pred);
+  return launch_boundary_scan(pred, T, nvid, row_off, seg_id, seg_start, seg_end, num_seg, s);
+}
+
+int segments_check_rows(int T, int nvid, const int* row_off, int* rows) {
+  FX_REQUIRE(nvid >= 1 && (row_off || T > 0), "segments: need T > 0 (or row offsets) and ncls > 0");
+  for (int v = 0; v < nvid; ++v) FX_REQUIRE(row_of(T, row_off, v + 1) > row_of(T, row_off, v), "segments: empty video");
+  *rows = row_of(T, row_off, nvid);
+  return FX_OK;
+}
+
+int launch_boundary_scan(const int32_t* pred, int T, int nvid, const int* row_off, int32_t* seg_id,
+                         int32_t* seg_start, int32_t* seg_end, int32_t* num_seg, hipStream_t s) {
   for (int c0 = 0; c0 < nvid; c0 += MAXV) {
     RowOff ro{};
     const int nv = std::min(MAXV, nvid - c0);

@@ -417,10 +417,197 @@ class ProcessFeatureFn(torch.autograd.Function):
         return dx, None
 
 
-def process_feature(x, n):
+class ProcessFeature2Fn(torch.autograd.Function):
+    """``Block.process_feature`` of the verb/noun model (blocks_SepVerbNoun.py:227-232): the last
+    n1 + n2 channels take two independent softmaxes (``logit2prob(..., class_sep=n1)``); same
+    outputs and gradient contract as ProcessFeatureFn."""
+
+    @staticmethod
+    def forward(ctx, x, n1, n2):
+        lib = nx.load()
+        rows, cols = x.shape
+        n = n1 + n2
+        out = _empty(rows, cols, device=x.device)
+        clogit = _empty(rows, n, device=x.device)
+        _check(lib.fx_process_feature2_fwd(nx.ptr(x), nx.ld(x), rows, cols, n1, n2, nx.ptr(out), cols, nx.ptr(clogit),
+                                           n, nx.stream()), "fx_process_feature2_fwd")
+        ctx.n = (n1, n2)
+        ctx.save_for_backward(out)
+        ctx.set_materialize_grads(False)
+        return out, clogit
+
+    @staticmethod
+    def backward(ctx, dout, dclogit):
+        lib = nx.load()
+        (out,) = ctx.saved_tensors
+        rows, cols = out.shape
+        n1, n2 = ctx.n
+        if dout is None:
+            dout = torch.zeros_like(out)
+        dout = dout.contiguous()
+        dclogit = None if dclogit is None else dclogit.contiguous()
+        dx = _empty(rows, cols, device=out.device)
+        _check(lib.fx_process_feature2_bwd(nx.ptr(out), cols, nx.ptr(dout), cols, nx.ptr(dclogit), n1 + n2, rows, cols,
+                                           n1, n2, nx.ptr(dx), cols, nx.stream()), "fx_process_feature2_bwd")
+        return dx, None, None
+
+
+def process_feature(x, n, class_sep=None):
     """Returns (feature-with-probs, class logits) like the reference (its clogit is a view of the
-    input; here it is a copy with the same values written by the same kernel)."""
-    return ProcessFeatureFn.apply(_2d(x), n)
+    input; here it is a copy with the same values written by the same kernel).  ``class_sep`` = n1:
+    the n class channels are a verb group of n1 and a noun group of n - n1, each with its own softmax."""
+    if class_sep is None or class_sep <= 0:
+        return ProcessFeatureFn.apply(_2d(x), n)
+    if class_sep >= n:
+        raise ValueError(f"process_feature: class_sep {class_sep} leaves no second group of {n} class channels")
+    return ProcessFeature2Fn.apply(_2d(x), int(class_sep), int(n - class_sep))
+
+
+# ---------------------------------------------------------------------------
+# verb / noun -> action log-probabilities (blocks_SepVerbNoun.py)
+# ---------------------------------------------------------------------------
+
+class VerbNounMap:
+    """The action -> (verb id, noun id) mapping of the verb/noun model (the reference's module globals
+    ``_VIDS`` / ``_NIDS``, blocks_SepVerbNoun.py:148-170) with what the kernels need, made once per
+    mapping and cached per device: the int32 id tables and, for the backward's scatter, the inverse
+    (CSR) lists -- for every verb bin and every noun bin its actions in ascending order."""
+
+    def __init__(self, vids, nids):
+        self.vids = [int(v) for v in vids]
+        self.nids = [int(n) for n in nids]
+        if not self.vids or len(self.vids) != len(self.nids):
+            raise ValueError(f"verb/noun map: {len(self.vids)} verb ids vs {len(self.nids)} noun ids")
+        if min(self.vids) < 0 or min(self.nids) < 0:
+            raise ValueError("verb/noun map: negative id")
+        self.num_actions = len(self.vids)
+        self.num_verbs = max(self.vids) + 1      # verb bins the mapping reaches
+        self.num_nouns = max(self.nids) + 1
+        self._host_csr = {}
+        self._tables = {}
+        self._csr = {}
+
+    def __len__(self):
+        return self.num_actions
+
+    @staticmethod
+    def _invert(ids, nbins):
+        bins = [[] for _ in range(nbins)]
+        for a, j in enumerate(ids):          # a ascending: every list comes out sorted
+            bins[j].append(a)
+        off = [0]
+        for b in bins:
+            off.append(off[-1] + len(b))
+        return off, [a for b in bins for a in b]
+
+    def check_heads(self, n1, n2):
+        if n1 < self.num_verbs or n2 < self.num_nouns:
+            raise ValueError(f"verb/noun map reaches verb {self.num_verbs - 1} / noun {self.num_nouns - 1}: "
+                             f"heads of {n1} / {n2} columns are too narrow")
+
+    def csr_host(self, n1, n2):
+        """(voff, vlist, noff, nlist) host lists for heads of n1 verb and n2 noun bins; a bin
+        without an action has an empty list (voff[j] == voff[j + 1])."""
+        key = (n1, n2)
+        if key not in self._host_csr:
+            self.check_heads(n1, n2)
+            self._host_csr[key] = self._invert(self.vids, n1) + self._invert(self.nids, n2)
+        return self._host_csr[key]
+
+    def tables(self, device):
+        """(vids, nids) int32 device tensors."""
+        device = torch.device(device)
+        t = self._tables.get(device)
+        if t is None:
+            t = self._tables[device] = (torch.tensor(self.vids, dtype=torch.int32, device=device),
+                                        torch.tensor(self.nids, dtype=torch.int32, device=device))
+        return t
+
+    def csr(self, device, n1, n2):
+        """The CSR lists of ``csr_host`` as int32 device tensors."""
+        key = (torch.device(device), n1, n2)
+        c = self._csr.get(key)
+        if c is None:
+            c = self._csr[key] = tuple(torch.tensor(x, dtype=torch.int32, device=key[0])
+                                       for x in self.csr_host(n1, n2))
+        return c
+
+    def verb_noun_of(self, actions):
+        """(verb ids, noun ids) int64 tensors of a tensor of action ids (the transcript embedding
+        lookup, blocks_SepVerbNoun.py:78-79)."""
+        v, n = self.tables(actions.device)
+        idx = actions.to(torch.int64)
+        return v[idx].to(torch.int64), n[idx].to(torch.int64)
+
+
+class VerbNounLogpFn(torch.autograd.Function):
+    """``combine_verb_noun_to_action(clogit, action=null, apply_log=True)``
+    (blocks_SepVerbNoun.py:189-224) on (R, n1 + n2) class logits -> (R, A (+ 1)) action
+    log-probabilities; backward through both log-softmaxes by the CSR gather kernel."""
+
+    @staticmethod
+    def forward(ctx, clogit, vnmap, n1, n2, null):
+        lib = nx.load()
+        R = clogit.shape[0]
+        A = vnmap.num_actions
+        dev = clogit.device
+        vids, nids = vnmap.tables(dev)
+        logp = _empty(R, A + null, device=dev)
+        lse = _empty(R, 2, device=dev)
+        _check(lib.fx_vn_logp_fwd(nx.ptr(clogit), nx.ld(clogit), R, n1, n2, nx.ptr(vids), nx.ptr(nids), A, null,
+                                  nx.ptr(logp), A + null, nx.ptr(lse), nx.stream()), "fx_vn_logp_fwd")
+        ctx.args = (vnmap, n1, n2, null)
+        ctx.save_for_backward(clogit, lse)
+        return logp
+
+    @staticmethod
+    def backward(ctx, dlogp):
+        lib = nx.load()
+        clogit, lse = ctx.saved_tensors
+        vnmap, n1, n2, null = ctx.args
+        R = clogit.shape[0]
+        A = vnmap.num_actions
+        dev = clogit.device
+        dlogp = dlogp.contiguous()
+        voff, vlist, noff, nlist = vnmap.csr(dev, n1, n2)
+        dcl = _empty(R, n1 + n2, device=dev)
+        _check(lib.fx_vn_logp_bwd(nx.ptr(clogit), nx.ld(clogit), nx.ptr(lse), nx.ptr(dlogp), A + null, R, n1, n2, A,
+                                  null, nx.ptr(voff), nx.ptr(vlist), nx.ptr(noff), nx.ptr(nlist), nx.ptr(dcl),
+                                  n1 + n2, nx.stream()), "fx_vn_logp_bwd")
+        return dcl, None, None, None, None
+
+
+def verb_noun_logp(clogit, vnmap, action=False):
+    """Action log-probabilities from verb/noun class logits (rows, n1 + n2).  ``action=False``: the
+    frame / segment heads, n1 / n2 = the mapping's verb / noun counts; ``action=True``: the token head
+    with a null bin closing each group (n1 = verbs + 1, n2 = nouns + 1) and a trailing null column in
+    the result.  The widths must fit the mapping exactly, as the reference asserts
+    (blocks_SepVerbNoun.py:198-207)."""
+    x = _2d(clogit)
+    k = 1 if action else 0
+    n1, n2 = vnmap.num_verbs + k, vnmap.num_nouns + k
+    if x.shape[1] != n1 + n2:
+        raise ValueError(f"verb_noun_logp: {x.shape[1]} class logits, the mapping needs {n1} + {n2}")
+    return VerbNounLogpFn.apply(x, vnmap, n1, n2, k)
+
+
+def segments_from_vn_probs(x2d, col0, n1, n2, vnmap):
+    """``segments_from_probs`` on the factorised probabilities: the per-frame argmax over
+    p_verb[vids[a]] * p_noun[nids[a]] (blocks_SepVerbNoun.py:285-296) and its run-length boundaries;
+    returns (S, seg_id, start, end) with one host read of S."""
+    lib = nx.load()
+    vnmap.check_heads(n1, n2)
+    T = x2d.shape[0]
+    dev = x2d.device
+    vids, nids = vnmap.tables(dev)
+    buf = torch.empty(4 * T + 1, device=dev, dtype=torch.int32)
+    pred, seg_id, st, en = buf[:T], buf[T:2 * T], buf[2 * T:3 * T], buf[3 * T:4 * T]
+    ns = buf[4 * T:]
+    _check(lib.fx_segments_from_vn_probs(nx.ptr(x2d), nx.ld(x2d), col0, n1, n2, nx.ptr(vids), nx.ptr(nids),
+                                         vnmap.num_actions, T, 1, None, nx.ptr(pred), nx.ptr(seg_id), nx.ptr(st),
+                                         nx.ptr(en), nx.ptr(ns), nx.stream()), "fx_segments_from_vn_probs")
+    S = int(ns.item())
+    return S, seg_id, st[:S], en[:S]
 
 
 # ---------------------------------------------------------------------------

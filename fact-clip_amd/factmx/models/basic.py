@@ -483,6 +483,13 @@ class TemporalDownsampleUpsample:
         S, seg_id, st, en = fxf.segments_from_probs(frame2d, col0, ncls)
         return cls(seg_id, st, en)
 
+    @classmethod
+    def from_vn_probs(cls, frame2d, col0, n1, n2, vnmap):
+        """The verb/noun model's segmentation (blocks_SepVerbNoun.py:285-296): argmax over
+        p_verb[vids[a]] * p_noun[nids[a]] of the n1 + n2 probability columns from col0."""
+        S, seg_id, st, en = fxf.segments_from_vn_probs(frame2d, col0, n1, n2, vnmap)
+        return cls(seg_id, st, en)
+
     @property
     def segs(self):
         if self._segs is None:

@@ -1,0 +1,349 @@
+"""The EPIC-Kitchens FACT with separate verb / noun class heads, with the reference's Python
+surface (fact_clip/models/blocks_SepVerbNoun.py).
+
+Same constructor, sub-module creation order, parameter names and shapes, block letters (``I``:
+InputBlockTDU, ``U``: UpdateBlockTDU) and side-channel attributes (``frame_logp``, ``seg_logp``,
+``action_logp``, ``tdu``, ``f2a_attn(_logit)``, ``a2f_attn(_logit)``).  Every action
+log-probability is ``log_softmax(verb)[VIDS[a]] + log_softmax(noun)[NIDS[a]]``; the action ->
+(verb, noun) tables live in a ``functional.VerbNounMap`` (the reference's module globals ``_VIDS`` /
+``_NIDS``), installed by ``init_VIDS_NIDS`` / ``set_verb_noun_ids`` / ``load_verb_noun_ids`` and
+captured by a model at construction.  Compute runs on the HIP kernels through factmx.functional;
+videos run one by one and the losses per video, as in the reference (no lockstep batch path).
+"""
+import torch
+import torch.nn as nn
+
+from .. import functional as fxf
+from ..configs.utils import update_from
+from . import basic
+from . import loss
+from .basic import time_mask, torch_class_label_to_segment_label
+from .blocks import _frame_pos
+from .loss import MatchCriterion
+
+_VNMAP = None     # the installed mapping (reference: _VIDS / _NIDS)
+
+MAPPING_FILES = ("./data/epic-kitchens/processed/mapping.txt",
+                 "./data/epic-kitchens/processed/verb_mapping.txt",
+                 "./data/epic-kitchens/processed/noun_mapping.txt")
+
+
+def set_verb_noun_ids(vids, nids):
+    """Install an action -> (verb id, noun id) mapping directly (lists indexed by action id)."""
+    global _VNMAP
+    _VNMAP = fxf.VerbNounMap(vids, nids)
+    return _VNMAP
+
+
+def load_verb_noun_ids(mapping, verb_mapping, noun_mapping):
+    """blocks_SepVerbNoun.py:154-170 with explicit paths: ``mapping`` lines are ``<id> <verb>,<noun>``,
+    the two word files ``<id> <name>``.  Installs and returns the mapping."""
+    from ..utils.dataset import load_action_mapping
+    v2i, _ = load_action_mapping(verb_mapping)
+    n2i, _ = load_action_mapping(noun_mapping)
+    vids, nids = [], []
+    with open(mapping) as fp:
+        lines = fp.read().split("\n")[:-1]
+    for line in lines:
+        _, aname = line.split(" ")
+        v, n = aname.split(",")
+        vids.append(v2i[v])
+        nids.append(n2i[n])
+    return set_verb_noun_ids(vids, nids)
+
+
+def init_VIDS_NIDS():
+    """blocks_SepVerbNoun.py:148-170: read the EPIC-Kitchens mapping files (relative to the working
+    directory, as the reference does) unless a mapping is installed already."""
+    if _VNMAP is None:
+        load_verb_noun_ids(*MAPPING_FILES)
+    return _VNMAP
+
+
+class FACT(nn.Module):
+    """blocks_SepVerbNoun.py:14-142."""
+
+    def __init__(self, cfg, in_dim, n_classes1=98, n_classes2=301):
+        super().__init__()
+        self.vnmap = init_VIDS_NIDS()
+        # the reference asserts this on every forward (blocks_SepVerbNoun.py:198-207)
+        if (n_classes1, n_classes2) != (self.vnmap.num_verbs, self.vnmap.num_nouns):
+            raise ValueError(f"{n_classes1} verb / {n_classes2} noun classes, but the installed mapping has "
+                             f"{self.vnmap.num_verbs} / {self.vnmap.num_nouns}")
+        self.cfg = cfg
+        self.num_classes1 = n_classes1   # verbs
+        self.num_classes2 = n_classes2   # nouns
+        base_cfg = cfg.Bi
+        self.frame_pe = basic.PositionalEncoding(base_cfg.hid_dim, max_len=10000, empty=(not cfg.FACT.fpos))
+        self.channel_masking_dropout = nn.Dropout2d(p=cfg.FACT.cmr)
+        if not cfg.FACT.trans:
+            self.action_query = nn.Parameter(torch.randn([cfg.FACT.ntoken, 1, base_cfg.a_dim]))
+        else:
+            self.action_pe = basic.PositionalEncoding(base_cfg.a_dim, max_len=1000)
+            self.verb_embed = nn.Embedding(n_classes1, base_cfg.a_dim // 2)
+            self.noun_embed = nn.Embedding(n_classes2, base_cfg.a_dim // 2)
+        block_list = []
+        for t in cfg.FACT.block:
+            if t == "I":
+                block = InputBlockTDU(cfg, in_dim, n_classes1, n_classes2, self.vnmap)
+            elif t == "U":
+                update_from(cfg.BU, base_cfg, inplace=True)
+                base_cfg = cfg.BU
+                block = UpdateBlockTDU(cfg, n_classes1, n_classes2, self.vnmap)
+            else:
+                raise ValueError(t)
+            block_list.append(block)
+        self.block_list = nn.ModuleList(block_list)
+        self.mcriterion = None
+
+    def _forward_one_video(self, seq, transcript=None):
+        frame_feature = seq
+        frame_pe = _frame_pos(self.frame_pe, seq)
+        if self.cfg.FACT.cmr and self.training:
+            frame_feature = self.channel_masking_dropout(frame_feature.permute([1, 2, 0])).permute([2, 0, 1])
+        if self.cfg.TM.use and self.training:
+            frame_feature = time_mask(frame_feature, self.cfg.TM.t, self.cfg.TM.m, self.cfg.TM.p,
+                                      replace_with_zero=True)
+        if not self.cfg.FACT.trans:
+            action_pe = self.action_query
+            action_feature = torch.zeros_like(action_pe)
+        else:
+            vtranscript, ntranscript = self.vnmap.verb_noun_of(transcript)
+            action_pe = self.action_pe(transcript)
+            vfeature = self.verb_embed(vtranscript).unsqueeze(1)
+            nfeature = self.noun_embed(ntranscript).unsqueeze(1)
+            action_feature = torch.cat([vfeature, nfeature], dim=-1) + action_pe
+            action_pe = torch.zeros_like(action_pe)
+        block_output = []
+        for block in self.block_list:
+            frame_feature, action_feature = block(frame_feature, action_feature, frame_pe, action_pe)
+            block_output.append((frame_feature, action_feature))
+        return block_output
+
+    def _loss_one_video(self, label):
+        mcriterion: MatchCriterion = self.mcriterion
+        mcriterion.set_label(label)
+        block = self.block_list[-1]
+        match = mcriterion.match(torch.exp(block.action_logp), block.a2f_attn)
+        self.loss_list = [blk.compute_loss(mcriterion, match) for blk in self.block_list]
+        return sum(self.loss_list) / len(self.loss_list)
+
+    def forward(self, seq_list, label_list, compute_loss=False):
+        save_list, final_loss, preds = [], [], []
+        for seq, label in zip(seq_list, label_list):
+            trans = torch_class_label_to_segment_label(label)[0] if self.cfg.FACT.trans else None
+            self._forward_one_video(seq.unsqueeze(1), trans)
+            preds.append(self.block_list[-1].eval(trans))
+            save_data = {}
+            save_list.append(save_data)
+            if compute_loss:
+                final_loss.append(self._loss_one_video(label))
+        # one read-back for every video's predictions, loss floats and the kernels' status word
+        dev = preds[0].device
+        parts = [p.reshape(-1).to(torch.float64) for p in preds]
+        parts += [lo.detach().reshape(1).to(torch.float64) for lo in final_loss]
+        if dev.type == "cuda":
+            parts.append(fxf.device_status(dev)[:1].to(torch.float64))
+        host = torch.cat(parts).cpu().numpy()
+        if dev.type == "cuda":
+            fxf.status_raise(int(host[-1]), dev)
+        off = 0
+        for save_data, p in zip(save_list, preds):
+            save_data["pred"] = host[off:off + p.numel()].astype("int64")
+            off += p.numel()
+        if compute_loss:
+            for save_data, lo in zip(save_list, host[off:off + len(final_loss)]):
+                save_data["loss"] = {"loss": float(lo)}
+            return sum(final_loss) / len(final_loss), save_list
+        return save_list
+
+    def save_model(self, fname):
+        torch.save(self.state_dict(), fname)
+
+
+class Block(nn.Module):
+    """blocks_SepVerbNoun.py:177-355."""
+
+    def __repr__(self):
+        return (f"{type(self).__name__}(\n  f:{self.frame_branch},\n  a:{self.action_branch},\n"
+                f"  a2f:{getattr(self, 'a2f_layer', None)},\n  f2a:{getattr(self, 'f2a_layer', None)}\n)")
+
+    def combine_verb_noun_to_action(self, clogit, action=False, apply_log=True):
+        """Action log-probabilities (T, 1, A (+ 1 null column)) of verb/noun class logits (T, 1, n1 + n2)."""
+        if not apply_log:
+            raise NotImplementedError("combine_verb_noun_to_action: only the log form is used (and built)")
+        return fxf.verb_noun_logp(clogit, self.vnmap, action=action).unsqueeze(1)
+
+    def process_feature(self, feature, nclass1, nclass2):
+        out, clogit = fxf.process_feature(feature, nclass1 + nclass2, class_sep=nclass1)
+        return out.unsqueeze(1), clogit.unsqueeze(1)
+
+    def create_fbranch(self, cfg, in_dim=None, f_inmap=False):
+        if in_dim is None:
+            in_dim = cfg.f_dim
+        if cfg.f == "m":
+            return basic.MSTCN(in_dim, cfg.f_dim, cfg.hid_dim, cfg.f_layers, dropout=cfg.dropout, ln=cfg.f_ln,
+                               ngroup=cfg.f_ngp, in_map=f_inmap)
+        if cfg.f == "m2":
+            return basic.MSTCN2(in_dim, cfg.f_dim, cfg.hid_dim, cfg.f_layers, dropout=cfg.dropout, ln=cfg.f_ln,
+                                ngroup=cfg.f_ngp, in_map=f_inmap)
+        raise ValueError(f"frame branch type {cfg.f!r} (the reference builds only 'm' / 'm2')")
+
+    def create_abranch(self, cfg):
+        if cfg.a == "sa":
+            layer = basic.SALayer(cfg.a_dim, cfg.a_nhead, dim_feedforward=cfg.a_ffdim, dropout=cfg.dropout,
+                                  attn_dropout=cfg.dropout)
+            return basic.SADecoder(cfg.a_dim, cfg.a_dim, cfg.hid_dim, layer, cfg.a_layers, in_map=False)
+        if cfg.a == "sca":
+            layer = basic.SCALayer(cfg.a_dim, cfg.hid_dim, cfg.a_nhead, cfg.a_ffdim, dropout=cfg.dropout,
+                                   attn_dropout=cfg.dropout)
+            norm = torch.nn.LayerNorm(cfg.a_dim)
+            return basic.SCADecoder(cfg.a_dim, cfg.a_dim, cfg.hid_dim, layer, cfg.a_layers, norm=norm, in_map=False)
+        if cfg.a in ("gru", "gru_om"):
+            assert self.cfg.FACT.trans
+            return basic.ActionUpdate_GRU(cfg.a_dim, cfg.a_dim, cfg.hid_dim, cfg.a_layers, dropout=cfg.dropout,
+                                          out_map=(cfg.a == "gru_om"))
+        raise ValueError(cfg.a)
+
+    def create_cross_attention(self, cfg, outdim, kq_pos=True):
+        return basic.X2Y_map(cfg.hid_dim, cfg.hid_dim, outdim, head_dim=cfg.hid_dim, dropout=cfg.dropout,
+                             kq_pos=kq_pos)
+
+    def action_token_loss(self, criterion: MatchCriterion, match, action_logp):
+        """blocks_SepVerbNoun.py:271-283: weighted one-hot NLL of the token log-probabilities, mean
+        over tokens (unmatched tokens target the null column)."""
+        logp = action_logp.squeeze(1)
+        aind, sind = criterion._dev_match(match, logp.device)
+        A, C = logp.shape[0], logp.shape[-1]
+        clabel = torch.zeros(A, C, dtype=torch.long, device=logp.device)
+        clabel[:, -1] = 1
+        clabel[aind] = 0
+        clabel[aind, criterion.transcript[sind]] = 1
+        return ((-logp * clabel) * criterion.cweight).sum(-1).mean()
+
+    def temporal_downsample(self, frame_feature):
+        n1, n2 = self.nclass1, self.nclass2
+        f2 = fxf._2d(frame_feature)
+        tdu = basic.TemporalDownsampleUpsample.from_vn_probs(f2, f2.shape[1] - n1 - n2, n1, n2, self.vnmap)
+        seg = tdu.feature_frame2seg(frame_feature)
+        seg = fxf.gru(self.seg_update, seg, relu=True)            # relu(seg_update(seg))
+        seg = fxf.linear(seg, self.seg_combine.weight, self.seg_combine.bias).unsqueeze(1)
+        seg, seg_clogit = self.process_feature(seg, n1, n2)
+        return tdu, seg, seg_clogit
+
+    def temporal_upsample(self, tdu, seg_feature, frame_feature):
+        lin = self.sf_merge[0]
+        y = fxf.SegMergeFn.apply(fxf._2d(seg_feature), fxf._2d(frame_feature), tdu.seg_id32, tdu.start32, tdu.end32,
+                                 lin.weight, lin.bias)
+        return y.unsqueeze(1)
+
+    def _save_logp(self, frame_clogit, seg_clogit, action_clogit, tdu):
+        self.seg_logp = self.combine_verb_noun_to_action(seg_clogit)
+        self.frame_logp = self.combine_verb_noun_to_action(frame_clogit)
+        self.action_logp = self.combine_verb_noun_to_action(action_clogit, action=True)
+        self.tdu = tdu
+
+    def _frame_seg_loss(self, criterion):
+        frame_loss = criterion.frame_loss(self.frame_logp.squeeze(1), is_logit=False) / 2
+        seg_loss = criterion.frame_loss_tdu(self.seg_logp, self.tdu, is_logit=False) / 2
+        sl = loss.smooth_loss(torch.transpose(self.frame_logp, 0, 1), is_logit=False)
+        return (frame_loss + seg_loss) / 2 + self.cfg.Loss.sw * sl
+
+    @staticmethod
+    def _eval(action_logp, a2f_attn, frame_logp, weight):
+        """blocks_SepVerbNoun.py:323-342 without a host sync: null tokens are masked to -inf before
+        the argmax over tokens (first maximum, as the reference's argmax over the non-null subset);
+        with no non-null token the frame branch decides alone."""
+        fprob = torch.exp(frame_logp.squeeze(1))
+        alp = action_logp.squeeze(1)
+        a2f = a2f_attn.squeeze(0)
+        is_tok = alp.argmax(1) != alp.shape[-1] - 1
+        masked = torch.where(is_tok[None, :], a2f, torch.full((), float("-inf"), device=a2f.device, dtype=a2f.dtype))
+        qtk_prob = torch.exp(alp[:, :-1])
+        qtk_prob = qtk_prob / qtk_prob.sum(-1, keepdim=True)
+        mixed = ((1 - weight) * qtk_prob[masked.argmax(-1)] + weight * fprob).argmax(1)
+        return torch.where(is_tok.any(), mixed, fprob.argmax(1))
+
+    @staticmethod
+    def _eval_w_transcript(transcript, a2f_attn):
+        n = len(transcript)
+        return transcript[a2f_attn[0, :, :n].argmax(1)]
+
+    def eval(self, transcript=None):
+        if not self.cfg.FACT.trans:
+            return self._eval(self.action_logp, self.a2f_attn, self.frame_logp, self.cfg.FACT.mwt)
+        return self._eval_w_transcript(transcript, self.a2f_attn)
+
+
+class InputBlockTDU(Block):
+    """blocks_SepVerbNoun.py:358-413."""
+
+    def __init__(self, cfg, in_dim, nclass1, nclass2, vnmap):
+        super().__init__()
+        self.cfg = cfg
+        self.nclass1 = nclass1
+        self.nclass2 = nclass2
+        self.vnmap = vnmap
+        bcfg = cfg.Bi
+        self.frame_branch = self.create_fbranch(bcfg, in_dim, f_inmap=True)
+        self.action_branch = self.create_abranch(bcfg)
+        self.seg_update = nn.GRU(bcfg.hid_dim, bcfg.hid_dim // 2, 2, bidirectional=True)
+        self.seg_combine = nn.Linear(bcfg.hid_dim, bcfg.hid_dim)
+
+    def forward(self, frame_feature, action_feature, frame_pos, action_pos):
+        frame_feature = self.frame_branch(frame_feature)
+        frame_feature, frame_clogit = self.process_feature(frame_feature, self.nclass1, self.nclass2)
+        tdu, seg_feature, seg_clogit = self.temporal_downsample(frame_feature)
+        seg_pos = None if frame_pos is None else frame_pos[tdu.centers()]
+        action_feature = self.action_branch(action_feature, seg_feature, pos=seg_pos, query_pos=action_pos)
+        action_feature, action_clogit = self.process_feature(action_feature, self.nclass1 + 1, self.nclass2 + 1)
+        self._save_logp(frame_clogit, seg_clogit, action_clogit, tdu)
+        self.f2a_attn = None
+        self.a2f_attn = None
+        return frame_feature, action_feature
+
+    def compute_loss(self, criterion: MatchCriterion, match=None):
+        atk_loss = self.action_token_loss(criterion, match, self.action_logp) / 2
+        return self._frame_seg_loss(criterion) + atk_loss
+
+
+class UpdateBlockTDU(Block):
+    """blocks_SepVerbNoun.py:415-496: segment-level update with temporal down/up-sampling."""
+
+    def __init__(self, cfg, nclass1, nclass2, vnmap):
+        super().__init__()
+        self.cfg = cfg
+        self.nclass1 = nclass1
+        self.nclass2 = nclass2
+        self.vnmap = vnmap
+        bcfg = cfg.BU
+        self.frame_branch = self.create_fbranch(bcfg)
+        self.seg_update = nn.GRU(bcfg.hid_dim, bcfg.hid_dim // 2, bcfg.s_layers, bidirectional=True)
+        self.seg_combine = nn.Linear(bcfg.hid_dim, bcfg.hid_dim)
+        self.f2a_layer = self.create_cross_attention(bcfg, bcfg.a_dim)
+        self.action_branch = self.create_abranch(bcfg)
+        self.a2f_layer = self.create_cross_attention(bcfg, bcfg.f_dim)
+        self.sf_merge = nn.Sequential(nn.Linear(bcfg.hid_dim + bcfg.f_dim, bcfg.f_dim), nn.ReLU())
+
+    def forward(self, frame_feature, action_feature, frame_pos, action_pos):
+        tdu, seg_feature, seg_clogit = self.temporal_downsample(frame_feature)
+        seg_pos = None if frame_pos is None else frame_pos[tdu.centers()]
+        action_feature = self.f2a_layer(seg_feature, action_feature, X_pos=seg_pos, Y_pos=action_pos)
+        action_feature = self.action_branch(action_feature, action_pos)
+        action_feature, action_clogit = self.process_feature(action_feature, self.nclass1 + 1, self.nclass2 + 1)
+        seg_feature = self.a2f_layer(action_feature, seg_feature, X_pos=action_pos, Y_pos=seg_pos)
+        frame_feature = self.temporal_upsample(tdu, seg_feature, frame_feature)
+        frame_feature = self.frame_branch(frame_feature)
+        frame_feature, frame_clogit = self.process_feature(frame_feature, self.nclass1, self.nclass2)
+        self._save_logp(frame_clogit, seg_clogit, action_clogit, tdu)
+        self.f2a_attn_logit = self.f2a_layer.attn_logit.squeeze(0).unsqueeze(0)
+        self.f2a_attn = tdu.attn_seg2frame(self.f2a_layer.attn[0].transpose(2, 1)).transpose(2, 1)
+        self.a2f_attn_logit = self.a2f_layer.attn_logit.squeeze(0).unsqueeze(0)
+        self.a2f_attn = tdu.attn_seg2frame(self.a2f_layer.attn[0])
+        return frame_feature, action_feature
+
+    def compute_loss(self, criterion: MatchCriterion, match=None):
+        atk_loss = self.action_token_loss(criterion, match, self.action_logp) / 2
+        f2a_loss = criterion.cross_attn_loss_tdu(match, torch.transpose(self.f2a_attn_logit, 1, 2), self.tdu, dim=1)
+        a2f_loss = criterion.cross_attn_loss_tdu(match, self.a2f_attn_logit, self.tdu, dim=2)
+        return self._frame_seg_loss(criterion) + atk_loss + f2a_loss + a2f_loss

@@ -12,7 +12,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FACTMX_LIB", os.path.join(_HERE, "_lib", "libfactmx.so"))
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 P = ctypes.c_void_p
 I = ctypes.c_int
@@ -152,6 +152,11 @@ SIGNATURES = {
     "fx_softmax_rows_bwd": (I, [P, L, P, L, P, L, I, I, F, P, L, P]),
     "fx_process_feature_fwd": (I, [P, L, I, I, I, P, L, P, L, P]),
     "fx_process_feature_bwd": (I, [P, L, P, L, P, L, I, I, I, P, L, P]),
+    "fx_process_feature2_fwd": (I, [P, L, I, I, I, I, P, L, P, L, P]),
+    "fx_process_feature2_bwd": (I, [P, L, P, L, P, L, I, I, I, I, P, L, P]),
+    "fx_vn_logp_fwd": (I, [P, L, I, I, I, P, P, I, I, P, L, P, P]),
+    "fx_vn_logp_bwd": (I, [P, L, P, P, L, I, I, I, I, I, P, P, P, P, P, L, P]),
+    "fx_segments_from_vn_probs": (I, [P, L, I, I, I, P, P, I, I, I, P, P, P, P, P, P, P]),
     "fx_l2norm_fwd": (I, [P, L, I, I, P, L, P, P]),
     "fx_l2norm_bwd": (I, [P, L, P, P, L, I, I, P, L, P]),
     "fx_relu_bwd": (I, [P, L, P, L, I, I, P, L, P]),

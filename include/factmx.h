@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define FX_ABI_VERSION 22
+#define FX_ABI_VERSION 23
 
 enum {
   FX_OK = 0,
@@ -449,6 +449,55 @@ int fx_process_feature_fwd(const float* x, long long ldx, int rows, int cols, in
 int fx_process_feature_bwd(const float* out, long long ldo, const float* dout, long long lddo,
                            const float* dclogit, long long lddc, int rows, int cols, int n, float* dx,
                            long long lddx, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Verb / noun class heads of the EPIC-Kitchens model (blocks_SepVerbNoun.py).
+ * All rows are independent; n1 + n2 <= 2048 head columns, A <= 12287 actions;
+ * rows == 0 launches nothing.  No float atomics: results are bitwise
+ * repeatable run to run.
+ * fx_process_feature2_fwd / _bwd: Block.process_feature with
+ *   logit2prob(..., class_sep=n1) (blocks_SepVerbNoun.py:227-232,
+ *   basic.py:56-65): as fx_process_feature_* with n = n1 + n2, the tail
+ *   taking two independent softmaxes (first n1 columns, then n2); clogit
+ *   (nullable, rows x (n1+n2)) and dclogit as there.
+ * fx_vn_logp_fwd: combine_verb_noun_to_action(apply_log=True)
+ *   (blocks_SepVerbNoun.py:189-224).  clogit (rows x (n1+n2), ldc); vids /
+ *   nids: device int32[A], action a = (verb vids[a] < n1, noun nids[a] < n2).
+ *   logp[r, a] = log_softmax(clogit[r, :n1])[vids[a]]
+ *              + log_softmax(clogit[r, n1:])[nids[a]]          (rows x A)
+ *   null != 0 (the token head, n1 = V+1, n2 = N+1; action=True,
+ *   blocks_SepVerbNoun.py:198-202, 220-222): a trailing column
+ *   lsv[r, n1-1] + lsn[r, n2-1] is appended (rows x (A+1)).
+ *   lse (rows x 2): the two log-sum-exps, saved for the backward.
+ * fx_vn_logp_bwd: dclogit[r, j] = sum_{a: vids[a] = j} g[r, a]
+ *   - softmax_v[r, j] * sum_a g[r, a] for the verb columns, the noun columns
+ *   alike; the null column's gradient goes to the last bin of each group.
+ *   The scatter is a gather through inverse (CSR) lists: voff (n1 + 1) /
+ *   vlist (A) = for every verb bin its actions in ascending order (a bin
+ *   without actions is empty), noff (n2 + 1) / nlist (A) for the nouns;
+ *   device int32.  Each bin is summed in ascending a, the null column last.
+ * fx_segments_from_vn_probs: temporal_downsample's argmax
+ *   (blocks_SepVerbNoun.py:285-296): pred[t] = argmax_a
+ *   x[t, col0 + vids[a]] * x[t, col0 + n1 + nids[a]] (fp32 product, first
+ *   maximum), then fx_segments_from_probs' boundary scan, video-local tables
+ *   and num_seg contract (nvid, uniform T or ragged row_off).
+ * ---------------------------------------------------------------------- */
+int fx_process_feature2_fwd(const float* x, long long ldx, int rows, int cols, int n1, int n2,
+                            float* out, long long ldo, float* clogit, long long ldc, void* stream);
+int fx_process_feature2_bwd(const float* out, long long ldo, const float* dout, long long lddo,
+                            const float* dclogit, long long lddc, int rows, int cols, int n1, int n2,
+                            float* dx, long long lddx, void* stream);
+int fx_vn_logp_fwd(const float* clogit, long long ldc, int rows, int n1, int n2, const int32_t* vids,
+                   const int32_t* nids, int A, int null, float* logp, long long ldl, float* lse,
+                   void* stream);
+int fx_vn_logp_bwd(const float* clogit, long long ldc, const float* lse, const float* dlogp,
+                   long long ldg, int rows, int n1, int n2, int A, int null, const int32_t* voff,
+                   const int32_t* vlist, const int32_t* noff, const int32_t* nlist, float* dclogit,
+                   long long lddc, void* stream);
+int fx_segments_from_vn_probs(const float* x, long long ldx, int col0, int n1, int n2,
+                              const int32_t* vids, const int32_t* nids, int A, int T, int nvid,
+                              const int* row_off, int32_t* pred, int32_t* seg_id, int32_t* seg_start,
+                              int32_t* seg_end, int32_t* num_seg, void* stream);
 
 /* ------------------------------------------------------------------------
  * F.normalize(dim=-1, eps=1e-12) (blocks.py:174) and its backward.
