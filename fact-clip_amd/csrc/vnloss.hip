@@ -1,0 +1,464 @@
+// Factorised loss terms and prediction of the verb/noun FACT (fact_clip/models/blocks_SepVerbNoun.py
+// with loss.py): every action log-probability is
+//   logp[r, a] = lsv[r, vids[a]] + lsn[r, nids[a]]      (lsv / lsn: log-softmax of the verb / noun heads)
+// so each term is computed from the n1 + n2 head values of a row staged in LDS, as verbnoun.hip stages
+// them; the rows x A table is never built.
+//   vn_loss fwd/bwd : frame_loss (loss.py:246-258) and Block.action_token_loss
+//                     (blocks_SepVerbNoun.py:271-283) with hard labels, frame_loss_tdu (260-277) with the
+//                     frame labels of each TDU segment, smooth_loss (8-18) over consecutive rows
+//   vn_eval_pred    : Block._eval (blocks_SepVerbNoun.py:323-342)
+// Layout: one 256-thread workgroup per row (frame, segment or token).
+// Determinism: no float atomics.  Reductions are wave shuffles in a fixed tree plus a fixed-order
+// combine of the 4 wave partials; per-row partial sums are added by one workgroup in a fixed order;
+// the backward's scatters are gathers (the VerbNounMap CSR lists for actions -> bins, a chunked
+// ascending loop for a segment's frames -> bins) -- bitwise repeatable run to run.
+#include <algorithm>
+#include <cmath>
+
+#include "fx_common.h"
+
+namespace fx {
+namespace {
+
+constexpr int VL_MAXH = 2048;       // n1 + n2 head columns staged per row
+constexpr int VL_THREADS = 256;
+constexpr int VL_MAXLDS = 60 * 1024;   // dynamic LDS of one workgroup
+
+__device__ inline float vl_wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ inline float vl_wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+// block-wide max / sum of one value per thread: wave tree, then the 4 partials in fixed order
+__device__ inline float vl_block_max(float v, float* part) {
+  v = vl_wave_max(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3]));
+}
+__device__ inline float vl_block_sum(float v, float* part) {
+  v = vl_wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((part[0] + part[1]) + part[2]) + part[3];
+}
+// first maximum of (value, index) pairs over the workgroup; index 0x7fffffff = none
+__device__ inline void vl_block_argmax(float& v, int& i, float* pv, int* pi) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(v, o, 64);
+    const int oi = __shfl_xor(i, o, 64);
+    if (ov > v || (ov == v && oi < i)) {
+      v = ov;
+      i = oi;
+    }
+  }
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) {
+    pv[threadIdx.x >> 6] = v;
+    pi[threadIdx.x >> 6] = i;
+  }
+  __syncthreads();
+  v = pv[0];
+  i = pi[0];
+#pragma unroll
+  for (int k = 1; k < 4; ++k)
+    if (pv[k] > v || (pv[k] == v && pi[k] < i)) {
+      v = pv[k];
+      i = pi[k];
+    }
+}
+
+__device__ inline float vl_block_lse(const float* sh, int n, float* part) {
+  float m = -INFINITY;
+  for (int c = threadIdx.x; c < n; c += VL_THREADS) m = fmaxf(m, sh[c]);
+  m = vl_block_max(m, part);
+  float s = 0.f;
+  for (int c = threadIdx.x; c < n; c += VL_THREADS) s += expf(sh[c] - m);
+  s = vl_block_sum(s, part);
+  return m + logf(s);
+}
+
+// sh[0, n1 + n2) = log-softmax of both groups of the row at cr (the same arithmetic as vn_logp_fwd_kernel)
+__device__ inline void vl_stage_row(const float* cr, int n1, int n2, float* sh, float* part, float* lv_out,
+                                    float* ln_out) {
+  const int n = n1 + n2;
+  __syncthreads();
+  for (int c = threadIdx.x; c < n; c += VL_THREADS) sh[c] = cr[c];
+  __syncthreads();
+  const float lv = vl_block_lse(sh, n1, part);
+  const float ln = vl_block_lse(sh + n1, n2, part);
+  __syncthreads();
+  for (int c = threadIdx.x; c < n; c += VL_THREADS) sh[c] -= (c < n1 ? lv : ln);
+  __syncthreads();
+  *lv_out = lv;
+  *ln_out = ln;
+}
+// the same from saved log-sum-exps
+__device__ inline void vl_stage_row_lse(const float* cr, int n1, int n2, float lv, float ln, float* sh) {
+  for (int c = threadIdx.x; c < n1 + n2; c += VL_THREADS) sh[c] = cr[c] - (c < n1 ? lv : ln);
+}
+
+// label y -> its verb / noun head columns and class weight (y == A with null heads: the two null bins)
+__device__ inline void vl_label(long long y, const int32_t* vids, const int32_t* nids, int A, int null, int n1,
+                                int n2, const float* w, int* v, int* k, float* wy) {
+  const int yy = (int)min(max(y, 0LL), (long long)(A + null - 1));
+  if (yy == A) {
+    *v = n1 - 1;
+    *k = n2 - 1;
+  } else {
+    *v = min(max(vids[yy], 0), n1 - 1);
+    *k = min(max(nids[yy], 0), n2 - 1);
+  }
+  *wy = w[yy];
+}
+
+struct VnLossArgs {
+  const float* clogit;   // (R, n1 + n2), leading stride ld
+  long long ld;
+  int R, n1, n2, A, null;
+  const int32_t* vids;
+  const int32_t* nids;
+  const long long* y;    // hard: (R) labels; segment: (ny) frame labels; null: no CE term
+  int ny;
+  const int32_t* seg_start;   // segment mode: (R) first / last frame of each row's segment
+  const int32_t* seg_end;
+  const float* w;        // (A + null) class weights
+  int smooth;
+};
+
+// part[2 r] = CE term of row r, part[2 r + 1] = sum_a min(d[r, a]^2, 16); lse (R, 2) saved
+__global__ __launch_bounds__(VL_THREADS) void vn_loss_fwd_kernel(VnLossArgs a, float* lse, float* partial) {
+  __shared__ float sh0[VL_MAXH];
+  __shared__ float sh1[VL_MAXH];
+  __shared__ float part[4];
+  const int r = blockIdx.x, tid = threadIdx.x;
+  const int n1 = a.n1, n2 = a.n2;
+  float lv, ln;
+  vl_stage_row(a.clogit + (long long)r * a.ld, n1, n2, sh0, part, &lv, &ln);
+  if (tid == 0) {
+    lse[2 * (long long)r] = lv;
+    lse[2 * (long long)r + 1] = ln;
+  }
+  float ce = 0.f;
+  if (a.y && !a.seg_start) {
+    if (tid == 0) {
+      int v, k;
+      float wy;
+      vl_label(a.y[r], a.vids, a.nids, a.A, a.null, n1, n2, a.w, &v, &k, &wy);
+      ce = -wy * (sh0[v] + sh0[n1 + k]);
+    }
+  } else if (a.y) {
+    const int s0 = min(max(a.seg_start[r], 0), a.ny - 1), e0 = min(max(a.seg_end[r], s0), a.ny - 1);
+    float t = 0.f;
+    for (int f = s0 + tid; f <= e0; f += VL_THREADS) {
+      int v, k;
+      float wy;
+      vl_label(a.y[f], a.vids, a.nids, a.A, a.null, n1, n2, a.w, &v, &k, &wy);
+      t += -wy * (sh0[v] + sh0[n1 + k]);
+    }
+    ce = vl_block_sum(t, part) / (float)(e0 - s0 + 1);
+  }
+  float sm = 0.f;
+  if (a.smooth && r + 1 < a.R) {
+    float l1, l2;
+    vl_stage_row(a.clogit + (long long)(r + 1) * a.ld, n1, n2, sh1, part, &l1, &l2);
+    float t = 0.f;
+    for (int c = tid; c < a.A; c += VL_THREADS) {
+      const int v = min(max(a.vids[c], 0), n1 - 1), k = n1 + min(max(a.nids[c], 0), n2 - 1);
+      const float d = (sh1[v] - sh0[v]) + (sh1[k] - sh0[k]);
+      t += fminf(d * d, 16.f);
+    }
+    sm = vl_block_sum(t, part);
+  }
+  if (tid == 0) {
+    partial[2 * (long long)r] = ce;
+    partial[2 * (long long)r + 1] = sm;
+  }
+}
+
+// out[0] = c0 * sum(part[2i]) + c1 * sum(part[2i+1]): every thread adds its rows in ascending order,
+// then the fixed tree (c1 == 0 drops the smooth term)
+__global__ __launch_bounds__(VL_THREADS) void vn_loss_finish_kernel(const float* partial, int n, float c0, float c1,
+                                                                    float* out) {
+  __shared__ float part[4];
+  float x = 0.f, y = 0.f;
+  for (int i = threadIdx.x; i < n; i += VL_THREADS) {
+    x += partial[2 * (long long)i];
+    y += partial[2 * (long long)i + 1];
+  }
+  x = vl_block_sum(x, part);
+  y = vl_block_sum(y, part);
+  if (threadIdx.x == 0) out[0] = c1 != 0.f ? c0 * x + c1 * y : c0 * x;
+}
+
+// dclogit[r, :] of c_ce * CE + c_sm * smooth.  Dynamic LDS: cur[n] acc[n], and with the smooth term
+// prv[n] nxt[n] ga[A] (the row's A action gradients live in LDS only)
+__global__ __launch_bounds__(VL_THREADS) void vn_loss_bwd_kernel(VnLossArgs a, const float* lse, const float* gout,
+                                                                 float c_ce, float c_sm, const int32_t* voff,
+                                                                 const int32_t* vlist, const int32_t* noff,
+                                                                 const int32_t* nlist, float* dcl, long long lddc) {
+  extern __shared__ float dyn[];
+  __shared__ float part[4];
+  __shared__ int cv[VL_THREADS], ck[VL_THREADS];
+  __shared__ float cw[VL_THREADS];
+  const int r = blockIdx.x, tid = threadIdx.x;
+  const int n1 = a.n1, n2 = a.n2, n = n1 + n2;
+  float* cur = dyn;
+  float* acc = dyn + n;
+  const float g_ce = gout[0] * c_ce, g_sm = gout[0] * c_sm;
+  vl_stage_row_lse(a.clogit + (long long)r * a.ld, n1, n2, lse[2 * (long long)r], lse[2 * (long long)r + 1], cur);
+  for (int j = tid; j < n; j += VL_THREADS) acc[j] = 0.f;
+  __syncthreads();
+  if (a.y && !a.seg_start) {
+    int v, k;
+    float wy;
+    vl_label(a.y[r], a.vids, a.nids, a.A, a.null, n1, n2, a.w, &v, &k, &wy);
+    for (int j = tid; j < n; j += VL_THREADS)
+      acc[j] = (g_ce * wy) * (expf(cur[j]) - ((j == v || j == n1 + k) ? 1.f : 0.f));
+  } else if (a.y) {
+    const int s0 = min(max(a.seg_start[r], 0), a.ny - 1), e0 = min(max(a.seg_end[r], s0), a.ny - 1);
+    float wtot = 0.f;
+    for (int base = s0; base <= e0; base += VL_THREADS) {   // the segment's frames in ascending chunks
+      const int cnt = min(VL_THREADS, e0 - base + 1);
+      __syncthreads();
+      if (tid < cnt) {
+        int v, k;
+        float wy;
+        vl_label(a.y[base + tid], a.vids, a.nids, a.A, a.null, n1, n2, a.w, &v, &k, &wy);
+        cv[tid] = v;
+        ck[tid] = n1 + k;
+        cw[tid] = wy;
+        wtot += wy;
+      }
+      __syncthreads();
+      for (int j = tid; j < n; j += VL_THREADS) {   // every bin adds its frames of the chunk in ascending order
+        const int* cb = j < n1 ? cv : ck;
+        float s = acc[j];
+        for (int i = 0; i < cnt; ++i)
+          if (cb[i] == j) s += cw[i];
+        acc[j] = s;
+      }
+    }
+    wtot = vl_block_sum(wtot, part);
+    const float gl = g_ce / (float)(e0 - s0 + 1);
+    for (int j = tid; j < n; j += VL_THREADS) acc[j] = gl * (wtot * expf(cur[j]) - acc[j]);
+  }
+  if (a.smooth) {
+    float* prv = dyn + 2 * n;
+    float* nxt = dyn + 3 * n;
+    float* ga = dyn + 4 * n;
+    const bool hp = r > 0, hn = r + 1 < a.R;
+    if (hp)
+      vl_stage_row_lse(a.clogit + (long long)(r - 1) * a.ld, n1, n2, lse[2 * (long long)(r - 1)],
+                       lse[2 * (long long)(r - 1) + 1], prv);
+    if (hn)
+      vl_stage_row_lse(a.clogit + (long long)(r + 1) * a.ld, n1, n2, lse[2 * (long long)(r + 1)],
+                       lse[2 * (long long)(r + 1) + 1], nxt);
+    __syncthreads();
+    float tot = 0.f;
+    for (int c = tid; c < a.A; c += VL_THREADS) {
+      const int v = min(max(a.vids[c], 0), n1 - 1), k = n1 + min(max(a.nids[c], 0), n2 - 1);
+      float g = 0.f;
+      if (hp) {
+        const float d = (cur[v] - prv[v]) + (cur[k] - prv[k]);
+        if (d * d <= 16.f) g += 2.f * d;
+      }
+      if (hn) {
+        const float d = (nxt[v] - cur[v]) + (nxt[k] - cur[k]);
+        if (d * d <= 16.f) g -= 2.f * d;
+      }
+      g *= g_sm;
+      ga[c] = g;
+      tot += g;
+    }
+    tot = vl_block_sum(tot, part);   // (its barriers also publish ga)
+    for (int j = tid; j < n; j += VL_THREADS) {
+      const bool verb = j < n1;
+      const int b = verb ? j : j - n1;
+      const int32_t* off = verb ? voff : noff;
+      const int32_t* lst = verb ? vlist : nlist;
+      float s = 0.f;
+      const int e = min(off[b + 1], a.A);
+      for (int i = max(off[b], 0); i < e; ++i) s += ga[min(max(lst[i], 0), a.A - 1)];
+      acc[j] += s - expf(cur[j]) * tot;
+    }
+  }
+  float* dr = dcl + (long long)r * lddc;
+  for (int j = tid; j < n; j += VL_THREADS) dr[j] = acc[j];   // (each thread reads back its own slots)
+}
+
+// ---------------------------------------------------------------- prediction
+// per token q: ws row q = log-softmax of the n1 + 1 / n2 + 1 token heads, then Z_q = sum_a exp(logp[q, a])
+// and is_tok (the null column is not the first maximum over the A + 1 columns)
+__global__ __launch_bounds__(VL_THREADS) void vn_eval_tok_kernel(const float* aclogit, long long lda, int n1, int n2,
+                                                                 const int32_t* vids, const int32_t* nids, int A,
+                                                                 float* ws, int wld) {
+  __shared__ float sh[VL_MAXH];
+  __shared__ float part[4];
+  const int q = blockIdx.x, tid = threadIdx.x;
+  const int m1 = n1 + 1, m2 = n2 + 1, m = m1 + m2;
+  float lv, ln;
+  vl_stage_row(aclogit + (long long)q * lda, m1, m2, sh, part, &lv, &ln);
+  float z = 0.f, best = -INFINITY;
+  for (int c = tid; c < A; c += VL_THREADS) {
+    const int v = min(max(vids[c], 0), n1 - 1), k = min(max(nids[c], 0), n2 - 1);
+    const float lp = sh[v] + sh[m1 + k];
+    z += expf(lp);
+    best = fmaxf(best, lp);
+  }
+  z = vl_block_sum(z, part);
+  best = vl_block_max(best, part);
+  float* wr = ws + (long long)q * wld;
+  for (int c = tid; c < m; c += VL_THREADS) wr[c] = sh[c];
+  if (tid == 0) {
+    wr[m] = z;
+    wr[m + 1] = (sh[m1 - 1] + sh[m - 1]) > best ? 0.f : 1.f;
+  }
+}
+
+// per frame t: the first maximum of its attention over the non-null tokens, then the first maximum over a
+// of (1 - w) exp(logp_q[tok, a]) / Z_tok + w exp(logp_f[t, a])  (no non-null token: of exp(logp_f[t, a]))
+__global__ __launch_bounds__(VL_THREADS) void vn_eval_frame_kernel(const float* fclogit, long long ldf, int n1, int n2,
+                                                                   const int32_t* vids, const int32_t* nids, int A,
+                                                                   const float* attn, long long ldattn,
+                                                                   const int32_t* seg_id, int nattn, int Q,
+                                                                   const float* ws, int wld, float w1, float w,
+                                                                   int32_t* pred) {
+  __shared__ float fl[VL_MAXH];
+  __shared__ float tk[VL_MAXH];
+  __shared__ float part[4];
+  __shared__ int parti[4];
+  const int t = blockIdx.x, tid = threadIdx.x;
+  const int m1 = n1 + 1, m = n1 + n2 + 2;
+  float lv, ln;
+  vl_stage_row(fclogit + (long long)t * ldf, n1, n2, fl, part, &lv, &ln);
+  const int arow = seg_id ? min(max(seg_id[t], 0), nattn - 1) : t;
+  const float* ar = attn + (long long)arow * ldattn;
+  float bv = -INFINITY;
+  int bq = 0x7fffffff;
+  for (int q = tid; q < Q; q += VL_THREADS) {
+    if (ws[(long long)q * wld + m + 1] == 0.f) continue;
+    const float x = ar[q];
+    if (bq == 0x7fffffff || x > bv) {   // threads visit increasing q: keeps the first max per thread
+      bv = x;
+      bq = q;
+    }
+  }
+  // a thread's candidate always beats "none"; among candidates the larger value, then the lower token
+  float key = bq == 0x7fffffff ? -INFINITY : bv;
+  vl_block_argmax(key, bq, part, parti);
+  const bool any = bq != 0x7fffffff;
+  float zinv_den = 1.f;
+  if (any) {
+    const float* wr = ws + (long long)bq * wld;
+    for (int c = tid; c < m; c += VL_THREADS) tk[c] = wr[c];
+    zinv_den = wr[m];
+  }
+  __syncthreads();
+  float best = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int c = tid; c < A; c += VL_THREADS) {
+    const int v = min(max(vids[c], 0), n1 - 1), k = min(max(nids[c], 0), n2 - 1);
+    const float lf = fl[v] + fl[n1 + k];
+    float p = expf(lf);
+    if (any) {
+      const float lq = tk[v] + tk[m1 + k];
+      p = __fadd_rn(__fmul_rn(w1, expf(lq) / zinv_den), __fmul_rn(w, p));
+    }
+    if (p > best) {
+      best = p;
+      bi = c;
+    }
+  }
+  vl_block_argmax(best, bi, part, parti);
+  if (tid == 0) pred[t] = bi == 0x7fffffff ? 0 : bi;
+}
+
+int vl_check(int n1, int n2, int A, int rows) {
+  FX_REQUIRE(n1 > 0 && n2 > 0 && n1 + n2 <= VL_MAXH, "vn_loss: need n1, n2 > 0 and n1 + n2 <= 2048");
+  FX_REQUIRE(A > 0 && rows >= 0, "vn_loss: need A > 0 actions and rows >= 0");
+  return FX_OK;
+}
+
+}  // namespace
+}  // namespace fx
+
+using namespace fx;
+
+extern "C" {
+
+long long fx_vn_workspace_floats(int loss_rows, int tokens, int n1, int n2) {
+  return 2LL * std::max(loss_rows, 0) + (long long)std::max(tokens, 0) * (n1 + n2 + 4);
+}
+
+int fx_vn_loss_fwd(const float* clogit, long long ld, int R, int n1, int n2, const int32_t* vids, const int32_t* nids,
+                   int A, int null, const long long* y, int ny, const int32_t* seg_start, const int32_t* seg_end,
+                   const float* w, float c_ce, float c_sm, float* lse, float* out, float* workspace, void* stream) {
+  FX_TRY(vl_check(n1, n2, A, R));
+  FX_REQUIRE(ld >= n1 + n2, "vn_loss: leading dimension shorter than the row");
+  FX_REQUIRE(out && workspace && (R == 0 || (clogit && vids && nids && lse)), "vn_loss: bad arguments");
+  FX_REQUIRE(!y || (w && ny > 0), "vn_loss: labels need class weights");
+  FX_REQUIRE(!seg_start == !seg_end && (!seg_start || y), "vn_loss: segment mode needs labels, starts and ends");
+  FX_REQUIRE(!y || seg_start || ny == R, "vn_loss: hard targets need one label per row");
+  hipStream_t s = (hipStream_t)stream;
+  VnLossArgs a{clogit, ld, R, n1, n2, A, null ? 1 : 0, vids, nids, y, ny, seg_start, seg_end, w, c_sm != 0.f};
+  if (R > 0) fx_launch(vn_loss_fwd_kernel, dim3(R), dim3(VL_THREADS), 0, s, a, lse, workspace);
+  fx_launch(vn_loss_finish_kernel, dim3(1), dim3(VL_THREADS), 0, s, (const float*)workspace, R, c_ce, c_sm, out);
+  FX_CHECK_HIP(hipGetLastError());
+  return FX_OK;
+}
+
+int fx_vn_loss_bwd(const float* clogit, long long ld, int R, int n1, int n2, const int32_t* vids, const int32_t* nids,
+                   int A, int null, const long long* y, int ny, const int32_t* seg_start, const int32_t* seg_end,
+                   const float* w, const int32_t* voff, const int32_t* vlist, const int32_t* noff,
+                   const int32_t* nlist, const float* lse, float c_ce, float c_sm, const float* gout, float* dclogit,
+                   long long lddc, void* stream) {
+  FX_TRY(vl_check(n1, n2, A, R));
+  FX_REQUIRE(ld >= n1 + n2 && lddc >= n1 + n2, "vn_loss: leading dimension shorter than the row");
+  if (R == 0) return FX_OK;
+  const int smooth = c_sm != 0.f;
+  FX_REQUIRE(clogit && vids && nids && lse && gout && dclogit, "vn_loss_bwd: bad arguments");
+  FX_REQUIRE(!y || (w && ny > 0), "vn_loss: labels need class weights");
+  FX_REQUIRE(!seg_start == !seg_end && (!seg_start || y), "vn_loss: segment mode needs labels, starts and ends");
+  FX_REQUIRE(!y || seg_start || ny == R, "vn_loss: hard targets need one label per row");
+  FX_REQUIRE(!smooth || (voff && vlist && noff && nlist), "vn_loss_bwd: the smooth term needs the CSR lists");
+  const long long floats = smooth ? 4LL * (n1 + n2) + A : 2LL * (n1 + n2);
+  FX_REQUIRE(floats * (long long)sizeof(float) <= VL_MAXLDS,
+             "vn_loss_bwd: the smooth term needs 4 (n1 + n2) + A <= 15360 floats of LDS");
+  VnLossArgs a{clogit, ld, R, n1, n2, A, null ? 1 : 0, vids, nids, y, ny, seg_start, seg_end, w, smooth};
+  fx_launch(vn_loss_bwd_kernel, dim3(R), dim3(VL_THREADS), (std::uint32_t)(floats * sizeof(float)),
+            (hipStream_t)stream, a, lse, gout, c_ce, c_sm, voff, vlist, noff, nlist, dclogit, lddc);
+  FX_CHECK_HIP(hipGetLastError());
+  return FX_OK;
+}
+
+int fx_vn_eval_pred(const float* action_clogit, long long lda, int Q, const float* frame_clogit, long long ldf, int T,
+                    int n1, int n2, const int32_t* vids, const int32_t* nids, int A, const float* attn,
+                    long long ldattn, const int32_t* seg_id, int nattn, float mwt, float* workspace, int32_t* pred,
+                    void* stream) {
+  FX_TRY(vl_check(n1, n2, A, T));
+  FX_REQUIRE(n1 + n2 + 2 <= VL_MAXH, "vn_eval_pred: need n1 + n2 + 2 <= 2048 token head columns");
+  FX_REQUIRE(Q > 0 && lda >= n1 + n2 + 2 && ldf >= n1 + n2 && ldattn >= Q, "vn_eval_pred: bad sizes");
+  FX_REQUIRE(seg_id ? nattn > 0 : nattn == T, "vn_eval_pred: frame-level attention needs one row per frame");
+  if (T == 0) return FX_OK;
+  FX_REQUIRE(action_clogit && frame_clogit && vids && nids && attn && workspace && pred, "vn_eval_pred: bad arguments");
+  hipStream_t s = (hipStream_t)stream;
+  const int wld = n1 + n2 + 4;
+  fx_launch(vn_eval_tok_kernel, dim3(Q), dim3(VL_THREADS), 0, s, action_clogit, lda, n1, n2, vids, nids, A, workspace,
+            wld);
+  const float w1 = (float)(1.0 - (double)mwt);
+  fx_launch(vn_eval_frame_kernel, dim3(T), dim3(VL_THREADS), 0, s, frame_clogit, ldf, n1, n2, vids, nids, A, attn,
+            ldattn, seg_id, nattn, Q, (const float*)workspace, wld, w1, mwt, pred);
+  FX_CHECK_HIP(hipGetLastError());
+  return FX_OK;
+}
+
+}  // extern "C"

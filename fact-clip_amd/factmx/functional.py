@@ -610,6 +610,136 @@ def segments_from_vn_probs(x2d, col0, n1, n2, vnmap):
     return S, seg_id, st[:S], en[:S]
 
 
+def _vn_heads(x, vnmap, action, what):
+    k = 1 if action else 0
+    n1, n2 = vnmap.num_verbs + k, vnmap.num_nouns + k
+    if x.shape[1] != n1 + n2:
+        raise ValueError(f"{what}: {x.shape[1]} class logits, the mapping needs {n1} + {n2}")
+    return n1, n2, k
+
+
+class VnClassLossFn(torch.autograd.Function):
+    """c_ce * sum(CE terms) + c_sm * sum(smooth terms) of the factorised action log-probabilities of
+    (R, n1 + n2) class logits as one scalar (fx_vn_loss_*): the (R, A) table is never built."""
+
+    @staticmethod
+    def forward(ctx, clogit, vnmap, n1, n2, null, y, seg_start, seg_end, w, c_ce, c_sm):
+        lib = nx.load()
+        R = clogit.shape[0]
+        A = vnmap.num_actions
+        dev = clogit.device
+        vids, nids = vnmap.tables(dev)
+        lse = _empty(R, 2, device=dev)
+        out = _empty(1, device=dev)
+        ws = _ws(lib.fx_vn_workspace_floats(R, 0, n1, n2), dev)
+        ny = 0 if y is None else int(y.shape[0])
+        _check(lib.fx_vn_loss_fwd(nx.ptr(clogit), nx.ld(clogit), R, n1, n2, nx.ptr(vids), nx.ptr(nids), A, null,
+                                  nx.ptr(y), ny, nx.ptr(seg_start), nx.ptr(seg_end), nx.ptr(w), float(c_ce),
+                                  float(c_sm), nx.ptr(lse), nx.ptr(out), nx.ptr(ws), nx.stream()), "fx_vn_loss_fwd")
+        ctx.args = (vnmap, n1, n2, null, float(c_ce), float(c_sm))
+        ctx.save_for_backward(clogit, y, seg_start, seg_end, w, lse)
+        return out.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = nx.load()
+        clogit, y, seg_start, seg_end, w, lse = ctx.saved_tensors
+        vnmap, n1, n2, null, c_ce, c_sm = ctx.args
+        R = clogit.shape[0]
+        A = vnmap.num_actions
+        dev = clogit.device
+        vids, nids = vnmap.tables(dev)
+        voff, vlist, noff, nlist = vnmap.csr(dev, n1, n2)
+        g = g.reshape(1).contiguous()
+        dcl = _empty(R, n1 + n2, device=dev)
+        ny = 0 if y is None else int(y.shape[0])
+        _check(lib.fx_vn_loss_bwd(nx.ptr(clogit), nx.ld(clogit), R, n1, n2, nx.ptr(vids), nx.ptr(nids), A, null,
+                                  nx.ptr(y), ny, nx.ptr(seg_start), nx.ptr(seg_end), nx.ptr(w), nx.ptr(voff),
+                                  nx.ptr(vlist), nx.ptr(noff), nx.ptr(nlist), nx.ptr(lse), c_ce, c_sm, nx.ptr(g),
+                                  nx.ptr(dcl), n1 + n2, nx.stream()), "fx_vn_loss_bwd")
+        return (dcl,) + (None,) * 10
+
+
+def _vn_labels(t, dev, hi, what):
+    """int64 labels on ``dev``; a host tensor is range-checked here (a device tensor is not read
+    back: the kernels clamp)."""
+    if not t.is_cuda and t.numel() and (int(t.min()) < 0 or int(t.max()) >= hi):
+        raise ValueError(f"vn_class_loss: {what} outside [0, {hi})")
+    return t.to(device=dev, dtype=torch.int64).contiguous()
+
+
+def vn_class_loss(clogit, vnmap, weight, *, target=None, frame_label=None, seg_start=None, seg_end=None, c_ce,
+                  c_sm=0.0, action=False):
+    """One fused loss term of the verb/noun heads, a 0-dim tensor:
+    ``c_ce * sum_r CE_r + c_sm * sum_{r < R-1, a} min((logp[r+1, a] - logp[r, a])^2, 16)`` with
+    ``logp = verb_noun_logp(clogit, vnmap, action)`` never materialised.  ``target`` (R) int64: hard
+    labels, CE_r = -weight[y_r] logp[r, y_r] (``action=True``: label A is the null column).
+    ``frame_label`` (T) with ``seg_start`` / ``seg_end`` (R) int32: the rows are TDU segments and
+    CE_s = mean over the segment's frames of -weight[y_t] logp[s, y_t].  The caller folds
+    1/denominator and the term's weight into ``c_ce`` / ``c_sm`` (``c_sm == 0``: no smooth term)."""
+    x = _2d(clogit)
+    n1, n2, k = _vn_heads(x, vnmap, action, "vn_class_loss")
+    R, A, dev = x.shape[0], vnmap.num_actions, x.device
+    if (target is None) == (frame_label is None):
+        raise ValueError("vn_class_loss: give either target or frame_label with seg_start / seg_end")
+    if weight.numel() < A + k:
+        raise ValueError(f"vn_class_loss: {weight.numel()} class weights for {A + k} classes")
+    w = weight.detach().to(device=dev, dtype=_f32).contiguous()
+    if target is not None:
+        if seg_start is not None or seg_end is not None:
+            raise ValueError("vn_class_loss: seg_start / seg_end go with frame_label")
+        if target.dim() != 1 or target.shape[0] != R:
+            raise ValueError(f"vn_class_loss: {tuple(target.shape)} targets for {R} rows")
+        y, st, en = _vn_labels(target, dev, A + k, "target"), None, None
+    else:
+        if seg_start is None or seg_end is None or seg_start.shape != (R,) or seg_end.shape != (R,):
+            raise ValueError(f"vn_class_loss: frame_label needs seg_start / seg_end of {R} segment rows")
+        if frame_label.dim() != 1 or frame_label.shape[0] == 0:
+            raise ValueError("vn_class_loss: frame_label must be a non-empty (T) tensor")
+        T = frame_label.shape[0]
+        y = _vn_labels(frame_label, dev, A + k, "frame_label")
+        if not seg_start.is_cuda and R and (int(seg_start.min()) < 0 or int(seg_end.max()) >= T
+                                            or bool((seg_end < seg_start).any())):
+            raise ValueError(f"vn_class_loss: segments outside the {T} frames")
+        st = seg_start.to(device=dev, dtype=torch.int32).contiguous()
+        en = seg_end.to(device=dev, dtype=torch.int32).contiguous()
+    return VnClassLossFn.apply(x, vnmap, n1, n2, k, y, st, en, w, float(c_ce), float(c_sm))
+
+
+def vn_eval_pred(action_clogit, frame_clogit, attn, vnmap, mwt, seg_id=None):
+    """``Block._eval`` of the verb/noun model (blocks_SepVerbNoun.py:323-342) from the class logits:
+    token heads (Q, V + 1 + N + 1), frame heads (T, V + N), token -> frame attention (T, Q) (or
+    (1, T, Q)), or the segment-level (S, Q) table with ``seg_id`` (T) int32.  Returns the (T) int64
+    prediction on the device, without a host sync."""
+    lib = nx.load()
+    xa, xf = _2d(action_clogit.detach()), _2d(frame_clogit.detach())
+    n1, n2, _ = _vn_heads(xf, vnmap, False, "vn_eval_pred (frame heads)")
+    _vn_heads(xa, vnmap, True, "vn_eval_pred (token heads)")
+    at = attn.detach()
+    if at.dim() == 3:
+        at = at.squeeze(0)
+    if at.dim() == 2 and at.stride(-1) != 1:
+        at = at.contiguous()
+    T, Q, dev = xf.shape[0], xa.shape[0], xf.device
+    if Q == 0 or at.dim() != 2 or at.shape[1] != Q:
+        raise ValueError(f"vn_eval_pred: attention {tuple(at.shape)} for {Q} tokens")
+    if seg_id is None:
+        if at.shape[0] != T:
+            raise ValueError(f"vn_eval_pred: {at.shape[0]} attention rows for {T} frames")
+        sid = None
+    else:
+        if seg_id.shape != (T,) or at.shape[0] == 0:
+            raise ValueError(f"vn_eval_pred: seg_id {tuple(seg_id.shape)} for {T} frames")
+        sid = seg_id.to(device=dev, dtype=torch.int32).contiguous()
+    vids, nids = vnmap.tables(dev)
+    pred = torch.empty(T, device=dev, dtype=torch.int32)
+    ws = _ws(lib.fx_vn_workspace_floats(0, Q, n1, n2), dev)
+    _check(lib.fx_vn_eval_pred(nx.ptr(xa), nx.ld(xa), Q, nx.ptr(xf), nx.ld(xf), T, n1, n2, nx.ptr(vids), nx.ptr(nids),
+                               vnmap.num_actions, nx.ptr(at), nx.ld(at), nx.ptr(sid), int(at.shape[0]), float(mwt),
+                               nx.ptr(ws), nx.ptr(pred), nx.stream()), "fx_vn_eval_pred")
+    return pred.to(torch.int64)
+
+
 # ---------------------------------------------------------------------------
 # L2 normalisation
 # ---------------------------------------------------------------------------

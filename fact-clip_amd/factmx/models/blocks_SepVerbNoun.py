@@ -9,6 +9,9 @@ log-probability is ``log_softmax(verb)[VIDS[a]] + log_softmax(noun)[NIDS[a]]``; 
 ``_NIDS``), installed by ``init_VIDS_NIDS`` / ``set_verb_noun_ids`` / ``load_verb_noun_ids`` and
 captured by a model at construction.  Compute runs on the HIP kernels through factmx.functional;
 videos run one by one and the losses per video, as in the reference (no lockstep batch path).
+With ``FUSED_LOSS`` the class terms of the loss and the prediction of CUDA inputs come straight from
+the class logits (functional.vn_class_loss / vn_eval_pred): ``frame_logp`` / ``seg_logp`` are then
+computed only when something reads them.
 """
 import torch
 import torch.nn as nn
@@ -18,10 +21,15 @@ from ..configs.utils import update_from
 from . import basic
 from . import loss
 from .basic import time_mask, torch_class_label_to_segment_label
-from .blocks import _frame_pos
+from .blocks import _frame_pos, _Lazy, _lazy_attr
 from .loss import MatchCriterion
 
 _VNMAP = None     # the installed mapping (reference: _VIDS / _NIDS)
+
+# The per-video loss terms and the prediction of CUDA inputs straight from the class logits
+# (functional.vn_class_loss / vn_eval_pred: no T x A table of action log-probabilities is built);
+# False: the eager forms on the materialised tables.
+FUSED_LOSS = True
 
 MAPPING_FILES = ("./data/epic-kitchens/processed/mapping.txt",
                  "./data/epic-kitchens/processed/verb_mapping.txt",
@@ -164,6 +172,10 @@ class FACT(nn.Module):
 class Block(nn.Module):
     """blocks_SepVerbNoun.py:177-355."""
 
+    # side-channel tables nothing on the fused path reads: built on first read
+    frame_logp = _lazy_attr("frame_logp")
+    seg_logp = _lazy_attr("seg_logp")
+
     def __repr__(self):
         return (f"{type(self).__name__}(\n  f:{self.frame_branch},\n  a:{self.action_branch},\n"
                 f"  a2f:{getattr(self, 'a2f_layer', None)},\n  f2a:{getattr(self, 'f2a_layer', None)}\n)")
@@ -238,12 +250,27 @@ class Block(nn.Module):
         return y.unsqueeze(1)
 
     def _save_logp(self, frame_clogit, seg_clogit, action_clogit, tdu):
-        self.seg_logp = self.combine_verb_noun_to_action(seg_clogit)
-        self.frame_logp = self.combine_verb_noun_to_action(frame_clogit)
+        self._fused = FUSED_LOSS and frame_clogit.is_cuda
+        self._clogits = (frame_clogit, seg_clogit, action_clogit) if self._fused else None
+        if self._fused:
+            self.seg_logp = _Lazy(lambda c=seg_clogit: self.combine_verb_noun_to_action(c))
+            self.frame_logp = _Lazy(lambda c=frame_clogit: self.combine_verb_noun_to_action(c))
+        else:
+            self.seg_logp = self.combine_verb_noun_to_action(seg_clogit)
+            self.frame_logp = self.combine_verb_noun_to_action(frame_clogit)
         self.action_logp = self.combine_verb_noun_to_action(action_clogit, action=True)
         self.tdu = tdu
 
+    def _token_loss(self, criterion: MatchCriterion, match):
+        if self._fused:
+            return criterion.vn_token_terms(match, self._clogits[2], self.vnmap)
+        return self.action_token_loss(criterion, match, self.action_logp)
+
     def _frame_seg_loss(self, criterion):
+        if self._fused:
+            # (frame_loss / 2 + frame_loss_tdu / 2) / 2 + sw * smooth_loss, two launch pairs
+            fl = criterion.vn_frame_terms(self._clogits[0], self.vnmap, ce_coef=0.25, sm_coef=self.cfg.Loss.sw)
+            return fl + criterion.vn_seg_terms(self._clogits[1], self.vnmap, self.tdu, ce_coef=0.25)
         frame_loss = criterion.frame_loss(self.frame_logp.squeeze(1), is_logit=False) / 2
         seg_loss = criterion.frame_loss_tdu(self.seg_logp, self.tdu, is_logit=False) / 2
         sl = loss.smooth_loss(torch.transpose(self.frame_logp, 0, 1), is_logit=False)
@@ -271,6 +298,9 @@ class Block(nn.Module):
 
     def eval(self, transcript=None):
         if not self.cfg.FACT.trans:
+            if self._fused:
+                return fxf.vn_eval_pred(self._clogits[2], self._clogits[0], self.a2f_attn, self.vnmap,
+                                        self.cfg.FACT.mwt)
             return self._eval(self.action_logp, self.a2f_attn, self.frame_logp, self.cfg.FACT.mwt)
         return self._eval_w_transcript(transcript, self.a2f_attn)
 
@@ -303,7 +333,7 @@ class InputBlockTDU(Block):
         return frame_feature, action_feature
 
     def compute_loss(self, criterion: MatchCriterion, match=None):
-        atk_loss = self.action_token_loss(criterion, match, self.action_logp) / 2
+        atk_loss = self._token_loss(criterion, match) / 2
         return self._frame_seg_loss(criterion) + atk_loss
 
 
@@ -343,7 +373,7 @@ class UpdateBlockTDU(Block):
         return frame_feature, action_feature
 
     def compute_loss(self, criterion: MatchCriterion, match=None):
-        atk_loss = self.action_token_loss(criterion, match, self.action_logp) / 2
+        atk_loss = self._token_loss(criterion, match) / 2
         f2a_loss = criterion.cross_attn_loss_tdu(match, torch.transpose(self.f2a_attn_logit, 1, 2), self.tdu, dim=1)
         a2f_loss = criterion.cross_attn_loss_tdu(match, self.a2f_attn_logit, self.tdu, dim=2)
         return self._frame_seg_loss(criterion) + atk_loss + f2a_loss + a2f_loss

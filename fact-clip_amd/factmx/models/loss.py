@@ -6,7 +6,9 @@ the reference); its cost matrix (tokens x GT segments) is built on the device
 and copied once.  The per-term losses run as fused HIP kernel pairs
 (functional.ClassLossFn / AttnLossFn); a lockstep batch of videos takes the
 whole loss phase through models/vloss.py instead (a handful of launches for
-every term of every video).
+every term of every video).  The verb/noun model's class terms (vn_*_terms) are
+computed from the verb / noun head logits without the frames x actions table
+(functional.vn_class_loss).
 """
 import numpy as np
 import torch
@@ -94,7 +96,7 @@ class MatchCriterion:
                 for i in self.bg_ids:
                     swn[self._transcript_np == i] = self.cfg.Loss.bgw
                 self._sweight_np = swn
-        self.onehot_class_label = _onehot(label, self.nclasses)
+        self._onehot_class_label = None      # (T, nclasses): built on first read
         self.onehot_seg_label = _onehot(self.seg_label, S)
         cw = torch.ones(self.nclasses + 1, device=dev)
         cw[-1] = self.cfg.Loss.nullw
@@ -108,6 +110,18 @@ class MatchCriterion:
                 sw = torch.where(self.transcript == i, torch.full_like(sw, self.cfg.Loss.bgw), sw)
         self.cweight, self.sweight = cw, sw
         self._match_cache = None
+
+    @property
+    def onehot_class_label(self):
+        """The (T, nclasses) fp32 one-hot of the frame labels, built on first read: the fused terms
+        never need it."""
+        if getattr(self, "_onehot_class_label", None) is None:
+            self._onehot_class_label = _onehot(self.class_label, self.nclasses)
+        return self._onehot_class_label
+
+    @onehot_class_label.setter
+    def onehot_class_label(self, value):
+        self._onehot_class_label = value
 
     def _label_to_onehot(self, label, nclass):
         return _onehot(label, nclass)
@@ -241,6 +255,42 @@ class MatchCriterion:
         c_sm = (sm_coef / ((R - 1) * Q) if R > 1 else float("inf")) if sm_coef else 0.0
         return fxf.AttnLossFn.apply(L, z.contiguous(), aind.tolist(), sind.tolist(), sw, axis, xe_coef / denom, c_sm)
 
+    # ---------------- verb / noun heads: the same terms from the class logits (no T x A table) ----------------
+    def vn_frame_terms(self, frame_clogit, vnmap, ce_coef=1.0, sm_coef=0.0):
+        """ce_coef * frame_loss(logp, is_logit=False) + sm_coef * smooth_loss(logp^T, is_logit=False) with
+        logp = verb_noun_logp(frame_clogit) (blocks_SepVerbNoun.py:298-307) as one fused term."""
+        x = frame_clogit.squeeze(1) if frame_clogit.dim() == 3 else frame_clogit
+        if not x.is_cuda:
+            lp = vn_logp_eager(x, vnmap)
+            sm = sm_coef * smooth_loss(lp.unsqueeze(0), is_logit=False) if sm_coef else 0.0
+            return ce_coef * self.frame_loss(lp, is_logit=False) + sm
+        R, A = x.shape[0], vnmap.num_actions
+        c_sm = (sm_coef / ((R - 1) * A) if R > 1 else float("inf")) if sm_coef else 0.0
+        return fxf.vn_class_loss(x, vnmap, self.cweight, target=self.class_label, c_ce=ce_coef / float(R), c_sm=c_sm)
+
+    def vn_seg_terms(self, seg_clogit, vnmap, tdu, ce_coef=1.0):
+        """ce_coef * frame_loss_tdu(logp, tdu, is_logit=False) with logp = verb_noun_logp(seg_clogit)
+        as one fused term: each segment row takes the labels of its own frames."""
+        x = seg_clogit.squeeze(1) if seg_clogit.dim() == 3 else seg_clogit
+        if not x.is_cuda:
+            return ce_coef * self.frame_loss_tdu(vn_logp_eager(x, vnmap).unsqueeze(1), tdu, is_logit=False)
+        return fxf.vn_class_loss(x, vnmap, self.cweight, frame_label=self.class_label, seg_start=tdu.start32,
+                                 seg_end=tdu.end32, c_ce=ce_coef / float(x.shape[0]))
+
+    def vn_token_terms(self, match, action_clogit, vnmap, coef=1.0):
+        """coef * Block.action_token_loss(match, logp) (blocks_SepVerbNoun.py:271-283) with
+        logp = verb_noun_logp(action_clogit, action=True) as one fused term: a matched token targets its
+        segment's action, every other token the null column; mean over the tokens."""
+        x = action_clogit.squeeze(1) if action_clogit.dim() == 3 else action_clogit
+        Q, A, dev = x.shape[0], vnmap.num_actions, x.device
+        aind, sind = self._dev_match(match, dev)
+        tgt = torch.full((Q,), A, dtype=torch.int64, device=dev)
+        tgt[aind] = self.transcript[sind].to(torch.int64)
+        if not x.is_cuda:
+            lp = vn_logp_eager(x, vnmap, action=True)
+            return coef * ((-lp * _onehot(tgt, A + 1)) * self.cweight).sum(-1).mean()
+        return fxf.vn_class_loss(x, vnmap, self.cweight, target=tgt, c_ce=coef / float(Q), action=True)
+
     def frame_loss(self, frame_clogit, is_logit=True):
         """loss.py:246-258."""
         lp = torch.log_softmax(frame_clogit, dim=-1) if is_logit else frame_clogit
@@ -254,6 +304,21 @@ class MatchCriterion:
         z = _zoom(tdu, self.onehot_class_label)
         w = self.cweight[:lp.shape[-1]]
         return (-lp * z * w).sum() / z.sum()
+
+
+def vn_logp_eager(clogit, vnmap, action=False):
+    """combine_verb_noun_to_action(apply_log=True) (blocks_SepVerbNoun.py:189-224) in eager torch: the
+    materialised (R, A (+ 1 null column)) table the CPU forms of the vn_*_terms work on."""
+    k = 1 if action else 0
+    n1, n2 = vnmap.num_verbs + k, vnmap.num_nouns + k
+    if clogit.shape[-1] != n1 + n2:
+        raise ValueError(f"vn_logp_eager: {clogit.shape[-1]} class logits, the mapping needs {n1} + {n2}")
+    lv, ln = torch.log_softmax(clogit[..., :n1], -1), torch.log_softmax(clogit[..., n1:], -1)
+    vids, nids = vnmap.tables(clogit.device)
+    lp = lv[..., vids.to(torch.int64)] + ln[..., nids.to(torch.int64)]
+    if action:
+        lp = torch.cat([lp, (lv[..., -1] + ln[..., -1]).unsqueeze(-1)], -1)
+    return lp
 
 
 def infonce_contrastive_loss(projected_embeddings, text_embeddings, labels, temperature=0.07):

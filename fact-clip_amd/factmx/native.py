@@ -12,7 +12,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FACTMX_LIB", os.path.join(_HERE, "_lib", "libfactmx.so"))
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 P = ctypes.c_void_p
 I = ctypes.c_int
@@ -157,6 +157,10 @@ SIGNATURES = {
     "fx_vn_logp_fwd": (I, [P, L, I, I, I, P, P, I, I, P, L, P, P]),
     "fx_vn_logp_bwd": (I, [P, L, P, P, L, I, I, I, I, I, P, P, P, P, P, L, P]),
     "fx_segments_from_vn_probs": (I, [P, L, I, I, I, P, P, I, I, I, P, P, P, P, P, P, P]),
+    "fx_vn_workspace_floats": (L, [I, I, I, I]),
+    "fx_vn_loss_fwd": (I, [P, L, I, I, I, P, P, I, I, P, I, P, P, P, F, F, P, P, P, P]),
+    "fx_vn_loss_bwd": (I, [P, L, I, I, I, P, P, I, I, P, I, P, P, P, P, P, P, P, P, F, F, P, P, L, P]),
+    "fx_vn_eval_pred": (I, [P, L, I, P, L, I, I, I, P, P, I, P, L, P, I, F, P, P, P]),
     "fx_l2norm_fwd": (I, [P, L, I, I, P, L, P, P]),
     "fx_l2norm_bwd": (I, [P, L, P, P, L, I, I, P, L, P]),
     "fx_relu_bwd": (I, [P, L, P, L, I, I, P, L, P]),

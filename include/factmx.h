@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define FX_ABI_VERSION 23
+#define FX_ABI_VERSION 24
 
 enum {
   FX_OK = 0,
@@ -498,6 +498,67 @@ int fx_segments_from_vn_probs(const float* x, long long ldx, int col0, int n1, i
                               const int32_t* vids, const int32_t* nids, int A, int T, int nvid,
                               const int* row_off, int32_t* pred, int32_t* seg_id, int32_t* seg_start,
                               int32_t* seg_end, int32_t* num_seg, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Factorised loss terms and prediction of the verb / noun model: computed
+ * from the n1 + n2 head logits of each row, the rows x A table of action
+ * log-probabilities is never built.  Rules as above (n1 + n2 <= 2048, ids
+ * clamped into their group, no float atomics, bitwise repeatable); one
+ * workgroup per row.  vids / nids / voff / vlist / noff / nlist as for
+ * fx_vn_logp_*.  workspace: fx_vn_workspace_floats(loss_rows, tokens, n1, n2)
+ * floats (loss entry points: (R, 0, ..); fx_vn_eval_pred: (0, Q, ..) with the
+ * frame heads' n1 / n2).
+ * fx_vn_loss_fwd: one scalar
+ *     out = c_ce * sum_r CE_r + c_sm * sum_{r < R-1} sum_a min(d[r, a]^2, 16)
+ *   like fx_class_loss_* (the caller folds 1/denominator and the term's
+ *   weight into c_*; c_sm == 0 skips the smooth term, y == NULL the CE term).
+ *   logp[r, a] = lsv[r, vids[a]] + lsn[r, nids[a]]; with null != 0 the heads
+ *   carry a closing null bin each and label A selects lsv[r, n1-1] +
+ *   lsn[r, n2-1].  w: A + null class weights.  Labels are clamped into
+ *   [0, A + null).
+ *   Hard targets (seg_start == NULL; frame_loss loss.py:246-258,
+ *   Block.action_token_loss blocks_SepVerbNoun.py:271-283): y int64 (ny = R),
+ *     CE_r = -w[y_r] logp[r, y_r].
+ *   Segment soft targets (frame_loss_tdu, loss.py:260-277): R segment rows,
+ *   y the ny frame labels, seg_start / seg_end (R) the first / last frame of
+ *   each segment (device int32):
+ *     CE_s = sum_{t in seg s} -w[y_t] logp[s, y_t] / len_s.
+ *   Smooth term (smooth_loss, loss.py:8-18):
+ *     d[r, a] = (lsv[r+1, v] - lsv[r, v]) + (lsn[r+1, n] - lsn[r, n]).
+ *   lse (R x 2) is saved for the backward.
+ * fx_vn_loss_bwd: dclogit (R x (n1+n2), lddc) of out, scaled by the upstream
+ *   scalar gradient gout (device).  CE: g (onehot - softmax) per group, a
+ *   segment's frames summed per bin in ascending order.  Smooth: row r's
+ *   action gradients c_sm (h(d[r-1, a]) - h(d[r, a])), h(d) = 2d if d^2 <= 16
+ *   else 0, are kept in LDS, summed per bin through the CSR lists and pushed
+ *   through both log-softmaxes (needs 4 (n1+n2) + A <= 15360 floats of LDS).
+ * fx_vn_eval_pred: Block._eval (blocks_SepVerbNoun.py:323-342).  action_clogit
+ *   (Q x (n1+n2+2)): token heads with their null bins; frame_clogit
+ *   (T x (n1+n2)).  A token is non-null unless the null column is the first
+ *   maximum of its A + 1 log-probabilities.  attn: frame level (T x Q,
+ *   seg_id == NULL, nattn == T) or segment level (nattn x Q) with seg_id (T)
+ *   frame -> row.  pred[t] = first maximum over a of
+ *     (1 - mwt) exp(logp_q[tok, a]) / sum_a' exp(logp_q[tok, a'])
+ *       + mwt exp(logp_f[t, a]),
+ *   tok = first maximum of attn over the non-null tokens; without a non-null
+ *   token the first maximum of exp(logp_f[t, a]).  Actions sharing a
+ *   (verb, noun) pair tie exactly: the lower id wins.
+ * ---------------------------------------------------------------------- */
+long long fx_vn_workspace_floats(int loss_rows, int tokens, int n1, int n2);
+int fx_vn_loss_fwd(const float* clogit, long long ld, int R, int n1, int n2, const int32_t* vids,
+                   const int32_t* nids, int A, int null, const long long* y, int ny,
+                   const int32_t* seg_start, const int32_t* seg_end, const float* w, float c_ce,
+                   float c_sm, float* lse, float* out, float* workspace, void* stream);
+int fx_vn_loss_bwd(const float* clogit, long long ld, int R, int n1, int n2, const int32_t* vids,
+                   const int32_t* nids, int A, int null, const long long* y, int ny,
+                   const int32_t* seg_start, const int32_t* seg_end, const float* w,
+                   const int32_t* voff, const int32_t* vlist, const int32_t* noff, const int32_t* nlist,
+                   const float* lse, float c_ce, float c_sm, const float* gout, float* dclogit,
+                   long long lddc, void* stream);
+int fx_vn_eval_pred(const float* action_clogit, long long lda, int Q, const float* frame_clogit,
+                    long long ldf, int T, int n1, int n2, const int32_t* vids, const int32_t* nids, int A,
+                    const float* attn, long long ldattn, const int32_t* seg_id, int nattn, float mwt,
+                    float* workspace, int32_t* pred, void* stream);
 
 /* ------------------------------------------------------------------------
  * F.normalize(dim=-1, eps=1e-12) (blocks.py:174) and its backward.
