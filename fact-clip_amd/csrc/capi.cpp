@@ -622,6 +622,7 @@ long long fx_struct_size(int which) {
     case 3: return (long long)sizeof(fx_loss_term);
     case 4: return (long long)sizeof(fx_video_attn);
     case 5: return (long long)sizeof(fx_mstcn2_params);
+    case 6: return (long long)sizeof(fx_vn_term);
     default: return -1;
   }
 }

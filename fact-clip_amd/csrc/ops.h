@@ -61,6 +61,12 @@ int launch_vn_logp_fwd(const float* clogit, long long ldc, int rows, int n1, int
 int launch_vn_logp_bwd(const float* clogit, long long ldc, const float* lse, const float* dlogp, long long ldg,
                        int rows, int n1, int n2, int A, int null, const int32_t* voff, const int32_t* vlist,
                        const int32_t* noff, const int32_t* nlist, float* dclogit, long long lddc, hipStream_t s);
+// the term table's FX_TERM_VNCLASS terms (vnloss.hip).  check_vn_terms: the host checks of those terms, their
+// *count (0: neither launch below is made) and *lds_floats, the backward's dynamic LDS
+int check_vn_terms(const fx_loss_term* terms_host, int nterms, bool bwd, int* count, long long* lds_floats);
+void launch_vn_terms_fwd(const fx_loss_term* terms_dev, int nterms, float* part, hipStream_t s);
+void launch_vn_terms_bwd(const fx_loss_term* terms_dev, int nterms, const float* gterm, long long lds_floats,
+                         hipStream_t s);
 int launch_segments_vn(const float* x, long long ldx, int col0, int n1, int n2, const int32_t* vids,
                        const int32_t* nids, int A, int T, int nvid, const int* row_off, int32_t* pred,
                        int32_t* seg_id, int32_t* seg_start, int32_t* seg_end, int32_t* num_seg, hipStream_t s);

@@ -316,6 +316,7 @@ __device__ __forceinline__ void wave_rows(int R, int wv, int& r0, int& r1, int& 
 __global__ __launch_bounds__(VT) void terms_fwd_kernel(const fx_loss_term* terms, float* part) {
   __shared__ float red[2][VT / 64];
   const fx_loss_term& t = terms[blockIdx.y];
+  if (t.kind == FX_TERM_VNCLASS) return;   // (vnloss.hip's launch writes this term's partials)
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int gw = blockIdx.x * (VT / 64) + wv;
   int r0, r1, b0, b1;
@@ -611,9 +612,12 @@ int fx_loss_terms_fwd(const fx_loss_term* terms_host, const fx_loss_term* terms_
   const int nb = FX_LOSS_NB;
   float* part = workspace;
   float* vals = workspace + 2LL * nb * nterms;
+  long long vn_lds = 0;
+  int vn = 0;
+  FX_TRY(check_vn_terms(terms_host, nterms, false, &vn, &vn_lds));
   for (int i = 0; i < nterms; ++i) {
     const fx_loss_term& t = terms_host[i];
-    FX_REQUIRE(t.kind >= 0 && t.kind <= 2, "loss_terms: unknown term kind");
+    FX_REQUIRE(t.kind >= 0 && t.kind <= FX_TERM_VNCLASS, "loss_terms: unknown term kind");
     FX_REQUIRE(t.R > 0 && t.C > 0 && t.x && t.lse, "loss_terms: empty term");
     FX_REQUIRE(t.kind != FX_TERM_ATTN || (t.K >= 0 && t.K <= FX_LOSS_MAXK && t.lse2 && t.colz &&
                                           (t.K == 0 || (t.ka && t.kgs && t.kge && t.ksw))),
@@ -632,6 +636,10 @@ int fx_loss_terms_fwd(const fx_loss_term* terms_host, const fx_loss_term* terms_
   }
   fx_launch(terms_fwd_kernel, dim3(nb, nterms), dim3(VT), 0, s, terms_dev, part);
   FX_CHECK_HIP(hipGetLastError());
+  if (vn > 0) {
+    launch_vn_terms_fwd(terms_dev, nterms, part, s);
+    FX_CHECK_HIP(hipGetLastError());
+  }
   fx_launch(terms_finish_kernel, dim3(nterms), dim3(FT), 0, s, terms_dev, part, nb, vals);
   FX_CHECK_HIP(hipGetLastError());
   fx_launch(combine_kernel, dim3(nout), dim3(64), 0, s, vals, coef_dev, nterms, nout, out);
@@ -644,12 +652,16 @@ int fx_loss_terms_bwd(const fx_loss_term* terms_host, const fx_loss_term* terms_
   FX_REQUIRE(terms_host && terms_dev && nterms > 0 && coef && gout && workspace, "loss_terms_bwd: bad arguments");
   hipStream_t s = (hipStream_t)stream;
   float* gterm = workspace;
+  long long vn_lds = 0;
+  int vn = 0;
+  FX_TRY(check_vn_terms(terms_host, nterms, true, &vn, &vn_lds));
   fx_launch(combine_bwd_kernel, dim3(cdiv(nterms, 64)), dim3(64), 0, s, gout, coef, nterms, nout, gterm);
   FX_CHECK_HIP(hipGetLastError());
   int maxC = 1;
-  bool has[3] = {false, false, false};
+  bool has[4] = {false, false, false, false};
   for (int i = 0; i < nterms; ++i) {
     const fx_loss_term& t = terms_host[i];
+    FX_REQUIRE(t.kind >= 0 && t.kind <= FX_TERM_VNCLASS, "loss_terms_bwd: unknown term kind");
     FX_REQUIRE(t.dx, "loss_terms_bwd: term without a gradient buffer");
     has[t.kind] = true;
     if (t.kind == FX_TERM_CLASS) maxC = std::max(maxC, t.C);
@@ -661,6 +673,10 @@ int fx_loss_terms_bwd(const fx_loss_term* terms_host, const fx_loss_term* terms_
   }
   if (has[FX_TERM_ATTN]) {
     fx_launch(terms_bwd_kernel, dim3(FX_LOSS_NB, nterms), dim3(VT), 0, s, terms_dev, gterm, (int)FX_TERM_ATTN);
+    FX_CHECK_HIP(hipGetLastError());
+  }
+  if (vn > 0) {
+    launch_vn_terms_bwd(terms_dev, nterms, gterm, vn_lds, s);
     FX_CHECK_HIP(hipGetLastError());
   }
   if (has[FX_TERM_INFONCE]) {

@@ -7,6 +7,10 @@
 //                     (blocks_SepVerbNoun.py:271-283) with hard labels, frame_loss_tdu (260-277) with the
 //                     frame labels of each TDU segment, smooth_loss (8-18) over consecutive rows
 //   vn_eval_pred    : Block._eval (blocks_SepVerbNoun.py:323-342)
+//   vn_terms fwd/bwd: the same loss rows as FX_TERM_VNCLASS terms of the loss term table (vloss.hip):
+//                     workgroup b of a term takes rows b, b + FX_LOSS_NB, ... in ascending order
+//   vn_match_cost   : MatchCriterion.match's cost (loss.py:108-153, soft IoU 91-106) from the token heads
+//                     and interval overlaps of the (segment-level) attention, no T x Q x G cube
 // Layout: one 256-thread workgroup per row (frame, segment or token).
 // Determinism: no float atomics.  Reductions are wave shuffles in a fixed tree plus a fixed-order
 // combine of the 4 wave partials; per-row partial sums are added by one workgroup in a fixed order;
@@ -126,7 +130,8 @@ struct VnLossArgs {
   int R, n1, n2, A, null;
   const int32_t* vids;
   const int32_t* nids;
-  const long long* y;    // hard: (R) labels; segment: (ny) frame labels; null: no CE term
+  const long long* y;    // hard: (R) labels; segment: (ny) frame labels; null (and y32 null): no CE term
+  const int32_t* y32;    // the same labels as int32 (the term table's form); used when y is null
   int ny;
   const int32_t* seg_start;   // segment mode: (R) first / last frame of each row's segment
   const int32_t* seg_end;
@@ -134,12 +139,14 @@ struct VnLossArgs {
   int smooth;
 };
 
-// part[2 r] = CE term of row r, part[2 r + 1] = sum_a min(d[r, a]^2, 16); lse (R, 2) saved
-__global__ __launch_bounds__(VL_THREADS) void vn_loss_fwd_kernel(VnLossArgs a, float* lse, float* partial) {
-  __shared__ float sh0[VL_MAXH];
-  __shared__ float sh1[VL_MAXH];
-  __shared__ float part[4];
-  const int r = blockIdx.x, tid = threadIdx.x;
+__device__ inline bool vl_has_y(const VnLossArgs& a) { return a.y || a.y32; }
+__device__ inline long long vl_y(const VnLossArgs& a, int i) { return a.y ? a.y[i] : (long long)a.y32[i]; }
+
+// row r of the loss: its two log-sum-exps go to lse[2 r], lse[2 r + 1]; *ce = CE term of the row, *sm =
+// sum_a min(d[r, a]^2, 16) (both valid on thread 0).  sh0 / sh1: VL_MAXH floats of LDS each
+__device__ inline void vl_fwd_row(const VnLossArgs& a, int r, float* sh0, float* sh1, float* part, float* lse,
+                                  float* ce_out, float* sm_out) {
+  const int tid = threadIdx.x;
   const int n1 = a.n1, n2 = a.n2;
   float lv, ln;
   vl_stage_row(a.clogit + (long long)r * a.ld, n1, n2, sh0, part, &lv, &ln);
@@ -148,20 +155,20 @@ __global__ __launch_bounds__(VL_THREADS) void vn_loss_fwd_kernel(VnLossArgs a, f
     lse[2 * (long long)r + 1] = ln;
   }
   float ce = 0.f;
-  if (a.y && !a.seg_start) {
+  if (vl_has_y(a) && !a.seg_start) {
     if (tid == 0) {
       int v, k;
       float wy;
-      vl_label(a.y[r], a.vids, a.nids, a.A, a.null, n1, n2, a.w, &v, &k, &wy);
+      vl_label(vl_y(a, r), a.vids, a.nids, a.A, a.null, n1, n2, a.w, &v, &k, &wy);
       ce = -wy * (sh0[v] + sh0[n1 + k]);
     }
-  } else if (a.y) {
+  } else if (vl_has_y(a)) {
     const int s0 = min(max(a.seg_start[r], 0), a.ny - 1), e0 = min(max(a.seg_end[r], s0), a.ny - 1);
     float t = 0.f;
     for (int f = s0 + tid; f <= e0; f += VL_THREADS) {
       int v, k;
       float wy;
-      vl_label(a.y[f], a.vids, a.nids, a.A, a.null, n1, n2, a.w, &v, &k, &wy);
+      vl_label(vl_y(a, f), a.vids, a.nids, a.A, a.null, n1, n2, a.w, &v, &k, &wy);
       t += -wy * (sh0[v] + sh0[n1 + k]);
     }
     ce = vl_block_sum(t, part) / (float)(e0 - s0 + 1);
@@ -178,7 +185,19 @@ __global__ __launch_bounds__(VL_THREADS) void vn_loss_fwd_kernel(VnLossArgs a, f
     }
     sm = vl_block_sum(t, part);
   }
-  if (tid == 0) {
+  *ce_out = ce;
+  *sm_out = sm;
+}
+
+// part[2 r] = CE term of row r, part[2 r + 1] = sum_a min(d[r, a]^2, 16); lse (R, 2) saved
+__global__ __launch_bounds__(VL_THREADS) void vn_loss_fwd_kernel(VnLossArgs a, float* lse, float* partial) {
+  __shared__ float sh0[VL_MAXH];
+  __shared__ float sh1[VL_MAXH];
+  __shared__ float part[4];
+  const int r = blockIdx.x;
+  float ce, sm;
+  vl_fwd_row(a, r, sh0, sh1, part, lse, &ce, &sm);
+  if (threadIdx.x == 0) {
     partial[2 * (long long)r] = ce;
     partial[2 * (long long)r + 1] = sm;
   }
@@ -199,31 +218,41 @@ __global__ __launch_bounds__(VL_THREADS) void vn_loss_finish_kernel(const float*
   if (threadIdx.x == 0) out[0] = c1 != 0.f ? c0 * x + c1 * y : c0 * x;
 }
 
-// dclogit[r, :] of c_ce * CE + c_sm * smooth.  Dynamic LDS: cur[n] acc[n], and with the smooth term
-// prv[n] nxt[n] ga[A] (the row's A action gradients live in LDS only)
-__global__ __launch_bounds__(VL_THREADS) void vn_loss_bwd_kernel(VnLossArgs a, const float* lse, const float* gout,
-                                                                 float c_ce, float c_sm, const int32_t* voff,
-                                                                 const int32_t* vlist, const int32_t* noff,
-                                                                 const int32_t* nlist, float* dcl, long long lddc) {
-  extern __shared__ float dyn[];
-  __shared__ float part[4];
-  __shared__ int cv[VL_THREADS], ck[VL_THREADS];
-  __shared__ float cw[VL_THREADS];
-  const int r = blockIdx.x, tid = threadIdx.x;
+// the CSR inverse lists of the mapping and the LDS chunk tables of a segment's frames (VL_THREADS each)
+struct VnBwdTabs {
+  const int32_t* voff;
+  const int32_t* vlist;
+  const int32_t* noff;
+  const int32_t* nlist;
+  float* part;
+  int* cv;
+  int* ck;
+  float* cw;
+};
+
+// dr[0, n) = dclogit[r, :] of g_ce * CE + g_sm * smooth.  dyn (LDS): cur[n] acc[n], and with the smooth term
+// prv[n] nxt[n] ga[A] (the row's A action gradients live in LDS only).  Ends behind a barrier: the caller
+// may go on to another row
+__device__ inline void vl_bwd_row(const VnLossArgs& a, int r, const float* lse, float g_ce, float g_sm,
+                                  const VnBwdTabs& tb, float* dyn, float* dr) {
+  const int32_t *voff = tb.voff, *vlist = tb.vlist, *noff = tb.noff, *nlist = tb.nlist;
+  float* part = tb.part;
+  int *cv = tb.cv, *ck = tb.ck;
+  float* cw = tb.cw;
+  const int tid = threadIdx.x;
   const int n1 = a.n1, n2 = a.n2, n = n1 + n2;
   float* cur = dyn;
   float* acc = dyn + n;
-  const float g_ce = gout[0] * c_ce, g_sm = gout[0] * c_sm;
   vl_stage_row_lse(a.clogit + (long long)r * a.ld, n1, n2, lse[2 * (long long)r], lse[2 * (long long)r + 1], cur);
   for (int j = tid; j < n; j += VL_THREADS) acc[j] = 0.f;
   __syncthreads();
-  if (a.y && !a.seg_start) {
+  if (vl_has_y(a) && !a.seg_start) {
     int v, k;
     float wy;
-    vl_label(a.y[r], a.vids, a.nids, a.A, a.null, n1, n2, a.w, &v, &k, &wy);
+    vl_label(vl_y(a, r), a.vids, a.nids, a.A, a.null, n1, n2, a.w, &v, &k, &wy);
     for (int j = tid; j < n; j += VL_THREADS)
       acc[j] = (g_ce * wy) * (expf(cur[j]) - ((j == v || j == n1 + k) ? 1.f : 0.f));
-  } else if (a.y) {
+  } else if (vl_has_y(a)) {
     const int s0 = min(max(a.seg_start[r], 0), a.ny - 1), e0 = min(max(a.seg_end[r], s0), a.ny - 1);
     float wtot = 0.f;
     for (int base = s0; base <= e0; base += VL_THREADS) {   // the segment's frames in ascending chunks
@@ -232,7 +261,7 @@ __global__ __launch_bounds__(VL_THREADS) void vn_loss_bwd_kernel(VnLossArgs a, c
       if (tid < cnt) {
         int v, k;
         float wy;
-        vl_label(a.y[base + tid], a.vids, a.nids, a.A, a.null, n1, n2, a.w, &v, &k, &wy);
+        vl_label(vl_y(a, base + tid), a.vids, a.nids, a.A, a.null, n1, n2, a.w, &v, &k, &wy);
         cv[tid] = v;
         ck[tid] = n1 + k;
         cw[tid] = wy;
@@ -291,8 +320,80 @@ __global__ __launch_bounds__(VL_THREADS) void vn_loss_bwd_kernel(VnLossArgs a, c
       acc[j] += s - expf(cur[j]) * tot;
     }
   }
-  float* dr = dcl + (long long)r * lddc;
   for (int j = tid; j < n; j += VL_THREADS) dr[j] = acc[j];   // (each thread reads back its own slots)
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(VL_THREADS) void vn_loss_bwd_kernel(VnLossArgs a, const float* lse, const float* gout,
+                                                                 float c_ce, float c_sm, const int32_t* voff,
+                                                                 const int32_t* vlist, const int32_t* noff,
+                                                                 const int32_t* nlist, float* dcl, long long lddc) {
+  extern __shared__ float dyn[];
+  __shared__ float part[4];
+  __shared__ int cv[VL_THREADS], ck[VL_THREADS];
+  __shared__ float cw[VL_THREADS];
+  const int r = blockIdx.x;
+  const VnBwdTabs tb{voff, vlist, noff, nlist, part, cv, ck, cw};
+  vl_bwd_row(a, r, lse, gout[0] * c_ce, gout[0] * c_sm, tb, dyn, dcl + (long long)r * lddc);
+}
+
+// ---------------------------------------------------------------- the term table's VNCLASS terms
+__device__ inline VnLossArgs vl_term_args(const fx_loss_term& t, const fx_vn_term& m) {
+  VnLossArgs a;
+  a.clogit = t.x;
+  a.ld = t.sr;
+  a.R = t.R;
+  a.n1 = m.n1;
+  a.n2 = m.n2;
+  a.A = m.A;
+  a.null = m.null ? 1 : 0;
+  a.vids = m.vids;
+  a.nids = m.nids;
+  a.y = nullptr;
+  a.y32 = t.y;
+  a.ny = t.rs ? t.D : t.R;
+  a.seg_start = t.rs;
+  a.seg_end = t.re;
+  a.w = t.w;
+  a.smooth = t.c_sm != 0.f;
+  return a;
+}
+
+// grid (FX_LOSS_NB, nterms): workgroup b of a VNCLASS term adds its rows b, b + FX_LOSS_NB, ... in ascending
+// order into the two partials terms_finish_kernel sums
+__global__ __launch_bounds__(VL_THREADS) void vn_terms_fwd_kernel(const fx_loss_term* terms, float* partial) {
+  __shared__ float sh0[VL_MAXH];
+  __shared__ float sh1[VL_MAXH];
+  __shared__ float part[4];
+  const fx_loss_term& t = terms[blockIdx.y];
+  if (t.kind != FX_TERM_VNCLASS) return;
+  const VnLossArgs a = vl_term_args(t, *t.vn);
+  float ce = 0.f, sm = 0.f;
+  for (int r = blockIdx.x; r < a.R; r += gridDim.x) {
+    float c, s;
+    vl_fwd_row(a, r, sh0, sh1, part, t.lse, &c, &s);
+    ce += c;
+    sm += s;
+  }
+  if (threadIdx.x == 0) {
+    partial[(t.slot * (long long)gridDim.x + blockIdx.x) * 2] = ce;
+    partial[(t.slot * (long long)gridDim.x + blockIdx.x) * 2 + 1] = sm;
+  }
+}
+
+__global__ __launch_bounds__(VL_THREADS) void vn_terms_bwd_kernel(const fx_loss_term* terms, const float* gterm) {
+  extern __shared__ float dyn[];
+  __shared__ float part[4];
+  __shared__ int cv[VL_THREADS], ck[VL_THREADS];
+  __shared__ float cw[VL_THREADS];
+  const fx_loss_term& t = terms[blockIdx.y];
+  if (t.kind != FX_TERM_VNCLASS) return;
+  const fx_vn_term& m = *t.vn;
+  const VnLossArgs a = vl_term_args(t, m);
+  const VnBwdTabs tb{m.voff, m.vlist, m.noff, m.nlist, part, cv, ck, cw};
+  const float g = gterm[blockIdx.y];
+  for (int r = blockIdx.x; r < a.R; r += gridDim.x)
+    vl_bwd_row(a, r, t.lse, g * t.c_ce, g * t.c_sm, tb, dyn, t.dx + (long long)r * t.dsr);
 }
 
 // ---------------------------------------------------------------- prediction
@@ -382,6 +483,81 @@ __global__ __launch_bounds__(VL_THREADS) void vn_eval_frame_kernel(const float* 
   if (tid == 0) pred[t] = bi == 0x7fffffff ? 0 : bi;
 }
 
+// ---------------------------------------------------------------- matching cost
+struct VnMatchArgs {
+  const float* aclogit;   // (Q, n1 + n2 + 2) token heads
+  long long lda;
+  int n1, n2, A;
+  const int32_t* vids;
+  const int32_t* nids;
+  const float* attn;      // (nattn, Q): TDU segment rows (seg_start / seg_end) or frames (seg_start null)
+  long long ldattn;
+  int nattn;
+  const int32_t* seg_start;
+  const int32_t* seg_end;
+  const int32_t* gs;      // (G) ground-truth segments, inclusive frames, and their actions
+  const int32_t* ge;
+  const int32_t* gl;
+  int G, T;
+  float pc, a2fc;
+};
+
+// One workgroup per token a.  Pass 1 leaves overlap[a, s] in cost[a, s]: segment-level attention, one
+// thread per ground-truth segment walks the TDU segments meeting it in ascending order (found by
+// bisection: O(S + G) products per token in all); frame-level attention, one wave per ground-truth
+// segment, lanes over its frames, fixed shuffle tree.  col_a = sum_s overlap[a, s] (every thread its
+// segments in ascending order, then the fixed tree).  Pass 2: the writer of each entry turns it into the cost.
+__global__ __launch_bounds__(VL_THREADS) void vn_match_cost_kernel(VnMatchArgs p, float* cost) {
+  __shared__ float sh[VL_MAXH];
+  __shared__ float part[4];
+  const int a = blockIdx.x, tid = threadIdx.x;
+  const int m1 = p.n1 + 1, m2 = p.n2 + 1;
+  float lv, ln;
+  vl_stage_row(p.aclogit + (long long)a * p.lda, m1, m2, sh, part, &lv, &ln);
+  float* crow = cost + (long long)a * p.G;
+  const float* acol = p.attn + a;
+  float colp = 0.f;
+  if (p.seg_start) {
+    for (int s = tid; s < p.G; s += VL_THREADS) {
+      const int g0 = p.gs[s], g1 = p.ge[s];
+      int lo = 0, hi = p.nattn;               // first TDU segment ending at or after g0
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (p.seg_end[mid] < g0) lo = mid + 1;
+        else hi = mid;
+      }
+      float ov = 0.f;
+      for (int j = lo; j < p.nattn && p.seg_start[j] <= g1; ++j) {
+        const int b0 = max(p.seg_start[j], g0), b1 = min(p.seg_end[j], g1);
+        if (b1 >= b0) ov += acol[(long long)j * p.ldattn] * (float)(b1 - b0 + 1);
+      }
+      crow[s] = ov;
+      colp += ov;
+    }
+  } else {
+    const int lane = tid & 63, wv = tid >> 6;
+    for (int s = wv; s < p.G; s += VL_THREADS / 64) {
+      const int g0 = max(p.gs[s], 0), g1 = min(p.ge[s], p.nattn - 1);
+      float ov = 0.f;
+      for (int t = g0 + lane; t <= g1; t += 64) ov += acol[(long long)t * p.ldattn];
+      ov = vl_wave_sum(ov);
+      if (lane == 0) {
+        crow[s] = ov;
+        colp += ov;
+      }
+    }
+  }
+  const float col = vl_block_sum(colp, part);   // (its barriers also publish pass 1's entries to the workgroup)
+  for (int s = tid; s < p.G; s += VL_THREADS) {
+    const float ov = crow[s];
+    const float den = ((float)(p.ge[s] - p.gs[s] + 1) + col) - ov;
+    const float iou = den != 0.f ? ov / den : 0.f;
+    const int y = min(max(p.gl[s], 0), p.A - 1);
+    const int v = min(max(p.vids[y], 0), p.n1 - 1), k = min(max(p.nids[y], 0), p.n2 - 1);
+    crow[s] = -p.pc * expf(sh[v] + sh[m1 + k]) - p.a2fc * iou;
+  }
+}
+
 int vl_check(int n1, int n2, int A, int rows) {
   FX_REQUIRE(n1 > 0 && n2 > 0 && n1 + n2 <= VL_MAXH, "vn_loss: need n1, n2 > 0 and n1 + n2 <= 2048");
   FX_REQUIRE(A > 0 && rows >= 0, "vn_loss: need A > 0 actions and rows >= 0");
@@ -389,6 +565,53 @@ int vl_check(int n1, int n2, int A, int rows) {
 }
 
 }  // namespace
+
+// The table's VNCLASS terms (fx_loss_terms_fwd / _bwd, vloss.hip): checks on the host copies before any launch
+// (check_vn_terms; a table without such a term, *count == 0, launches nothing of this file), then one
+// launch over (FX_LOSS_NB, nterms); workgroups of the other kinds return at once.
+static int vn_terms_check(const fx_loss_term& t, bool bwd, long long* lds_floats) {
+  const fx_vn_term* m = t.vn_host;
+  FX_REQUIRE(m && t.vn, "loss_terms: VNCLASS term without its mapping");
+  FX_TRY(vl_check(m->n1, m->n2, m->A, t.R));
+  FX_REQUIRE(t.C == m->n1 + m->n2 && t.sc == 1 && t.sr >= t.C, "loss_terms: VNCLASS term needs rows of n1 + n2 logits");
+  FX_REQUIRE(m->vids && m->nids, "loss_terms: VNCLASS mapping without id tables");
+  FX_REQUIRE(!t.y || t.w, "loss_terms: VNCLASS labels need class weights");
+  FX_REQUIRE(!t.rs == !t.re && (!t.rs || (t.y && t.D > 0)),
+             "loss_terms: VNCLASS segment targets need frame labels, their count, starts and ends");
+  const bool smooth = t.c_sm != 0.f;
+  if (bwd) {
+    FX_REQUIRE(t.dx && t.dsc == 1 && t.dsr >= t.C, "loss_terms_bwd: VNCLASS term needs a row-major gradient buffer");
+    FX_REQUIRE(!smooth || (m->voff && m->vlist && m->noff && m->nlist),
+               "loss_terms_bwd: the VNCLASS smooth term needs the CSR lists");
+    const long long floats = smooth ? 4LL * t.C + m->A : 2LL * t.C;
+    FX_REQUIRE(floats * (long long)sizeof(float) <= VL_MAXLDS,
+               "loss_terms_bwd: the VNCLASS smooth term needs 4 (n1 + n2) + A <= 15360 floats of LDS");
+    *lds_floats = std::max(*lds_floats, floats);
+  }
+  return FX_OK;
+}
+
+int check_vn_terms(const fx_loss_term* terms_host, int nterms, bool bwd, int* count, long long* lds_floats) {
+  *count = 0;
+  *lds_floats = 0;
+  for (int i = 0; i < nterms; ++i) {
+    if (terms_host[i].kind != FX_TERM_VNCLASS) continue;
+    FX_TRY(vn_terms_check(terms_host[i], bwd, lds_floats));
+    ++*count;
+  }
+  return FX_OK;
+}
+
+void launch_vn_terms_fwd(const fx_loss_term* terms_dev, int nterms, float* part, hipStream_t s) {
+  fx_launch(vn_terms_fwd_kernel, dim3(FX_LOSS_NB, nterms), dim3(VL_THREADS), 0, s, terms_dev, part);
+}
+
+void launch_vn_terms_bwd(const fx_loss_term* terms_dev, int nterms, const float* gterm, long long lds_floats,
+                         hipStream_t s) {
+  fx_launch(vn_terms_bwd_kernel, dim3(FX_LOSS_NB, nterms), dim3(VL_THREADS),
+            (std::uint32_t)(lds_floats * sizeof(float)), s, terms_dev, gterm);
+}
+
 }  // namespace fx
 
 using namespace fx;
@@ -409,7 +632,7 @@ int fx_vn_loss_fwd(const float* clogit, long long ld, int R, int n1, int n2, con
   FX_REQUIRE(!seg_start == !seg_end && (!seg_start || y), "vn_loss: segment mode needs labels, starts and ends");
   FX_REQUIRE(!y || seg_start || ny == R, "vn_loss: hard targets need one label per row");
   hipStream_t s = (hipStream_t)stream;
-  VnLossArgs a{clogit, ld, R, n1, n2, A, null ? 1 : 0, vids, nids, y, ny, seg_start, seg_end, w, c_sm != 0.f};
+  VnLossArgs a{clogit, ld, R, n1, n2, A, null ? 1 : 0, vids, nids, y, nullptr, ny, seg_start, seg_end, w, c_sm != 0.f};
   if (R > 0) fx_launch(vn_loss_fwd_kernel, dim3(R), dim3(VL_THREADS), 0, s, a, lse, workspace);
   fx_launch(vn_loss_finish_kernel, dim3(1), dim3(VL_THREADS), 0, s, (const float*)workspace, R, c_ce, c_sm, out);
   FX_CHECK_HIP(hipGetLastError());
@@ -433,7 +656,7 @@ int fx_vn_loss_bwd(const float* clogit, long long ld, int R, int n1, int n2, con
   const long long floats = smooth ? 4LL * (n1 + n2) + A : 2LL * (n1 + n2);
   FX_REQUIRE(floats * (long long)sizeof(float) <= VL_MAXLDS,
              "vn_loss_bwd: the smooth term needs 4 (n1 + n2) + A <= 15360 floats of LDS");
-  VnLossArgs a{clogit, ld, R, n1, n2, A, null ? 1 : 0, vids, nids, y, ny, seg_start, seg_end, w, smooth};
+  VnLossArgs a{clogit, ld, R, n1, n2, A, null ? 1 : 0, vids, nids, y, nullptr, ny, seg_start, seg_end, w, smooth};
   fx_launch(vn_loss_bwd_kernel, dim3(R), dim3(VL_THREADS), (std::uint32_t)(floats * sizeof(float)),
             (hipStream_t)stream, a, lse, gout, c_ce, c_sm, voff, vlist, noff, nlist, dclogit, lddc);
   FX_CHECK_HIP(hipGetLastError());
@@ -457,6 +680,26 @@ int fx_vn_eval_pred(const float* action_clogit, long long lda, int Q, const floa
   const float w1 = (float)(1.0 - (double)mwt);
   fx_launch(vn_eval_frame_kernel, dim3(T), dim3(VL_THREADS), 0, s, frame_clogit, ldf, n1, n2, vids, nids, A, attn,
             ldattn, seg_id, nattn, Q, (const float*)workspace, wld, w1, mwt, pred);
+  FX_CHECK_HIP(hipGetLastError());
+  return FX_OK;
+}
+
+int fx_vn_match_cost(const float* action_clogit, long long lda, int Q, int n1, int n2, const int32_t* vids,
+                     const int32_t* nids, int A, const float* attn, long long ldattn, int nattn,
+                     const int32_t* seg_start, const int32_t* seg_end, const int32_t* gs, const int32_t* ge,
+                     const int32_t* gl, int G, int T, float pc, float a2fc, float* cost, void* stream) {
+  FX_TRY(vl_check(n1, n2, A, Q));
+  FX_REQUIRE(n1 + n2 + 2 <= VL_MAXH, "vn_match_cost: need n1 + n2 + 2 <= 2048 token head columns");
+  FX_REQUIRE(G > 0 && T > 0 && nattn > 0, "vn_match_cost: need ground-truth segments, frames and attention rows");
+  FX_REQUIRE(lda >= n1 + n2 + 2 && ldattn >= Q, "vn_match_cost: leading dimension shorter than the row");
+  FX_REQUIRE(!seg_start == !seg_end, "vn_match_cost: segment-level attention needs starts and ends");
+  FX_REQUIRE(seg_start ? nattn <= T : nattn == T,
+             "vn_match_cost: frame-level attention needs one row per frame, segment-level at most T rows");
+  if (Q == 0) return FX_OK;
+  FX_REQUIRE(action_clogit && vids && nids && attn && gs && ge && gl && cost, "vn_match_cost: bad arguments");
+  VnMatchArgs p{action_clogit, lda, n1, n2, A, vids, nids, attn, ldattn, nattn, seg_start, seg_end, gs, ge, gl, G, T,
+                pc, a2fc};
+  fx_launch(vn_match_cost_kernel, dim3(Q), dim3(VL_THREADS), 0, (hipStream_t)stream, p, cost);
   FX_CHECK_HIP(hipGetLastError());
   return FX_OK;
 }

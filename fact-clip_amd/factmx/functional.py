@@ -740,6 +740,50 @@ def vn_eval_pred(action_clogit, frame_clogit, attn, vnmap, mwt, seg_id=None):
     return pred.to(torch.int64)
 
 
+def vn_match_cost(action_clogit, attn, vnmap, gs, ge, gl, T, pc, a2fc, seg_start=None, seg_end=None):
+    """The matching cost of one video of the verb/noun model (MatchCriterion.match, loss.py:108-153 with
+    a2f_soft_iou 91-106) from the token heads (Q, V + 1 + N + 1): ``-pc * exp(logp[a, gl[s]]) - a2fc *
+    softIoU[a, s]`` as a (Q, G) fp32 device tensor.  ``attn``: the token -> frame attention (T, Q) (or
+    (1, T, Q)), or the segment-level (S, Q) rows with the TDU intervals ``seg_start`` / ``seg_end`` (S)
+    int32.  ``gs`` / ``ge`` / ``gl`` (G) int32: the ground-truth segments (inclusive frames) and their
+    actions.  No frames x tokens x segments intermediate is built."""
+    lib = nx.load()
+    xa = _2d(action_clogit.detach())
+    n1, n2, _ = _vn_heads(xa, vnmap, True, "vn_match_cost (token heads)")
+    n1, n2 = n1 - 1, n2 - 1
+    at = attn.detach()
+    if at.dim() == 3:
+        at = at.squeeze(0)
+    if at.dim() == 2 and at.stride(-1) != 1:
+        at = at.contiguous()
+    Q, dev = xa.shape[0], xa.device
+    if at.dim() != 2 or at.shape[1] != Q or at.shape[0] == 0:
+        raise ValueError(f"vn_match_cost: attention {tuple(at.shape)} for {Q} tokens")
+    if (seg_start is None) != (seg_end is None):
+        raise ValueError("vn_match_cost: seg_start and seg_end go together")
+    rows = int(at.shape[0])
+    if seg_start is None:
+        if rows != T:
+            raise ValueError(f"vn_match_cost: {rows} attention rows for {T} frames")
+        st = en = None
+    else:
+        if seg_start.shape != (rows,) or seg_end.shape != (rows,) or rows > T:
+            raise ValueError(f"vn_match_cost: {rows} segment rows need {rows} starts and ends within {T} frames")
+        st = seg_start.to(device=dev, dtype=torch.int32).contiguous()
+        en = seg_end.to(device=dev, dtype=torch.int32).contiguous()
+    G = int(gs.shape[0])
+    if G == 0 or gs.shape != (G,) or ge.shape != (G,) or gl.shape != (G,):
+        raise ValueError("vn_match_cost: gs / ge / gl must be non-empty (G) tensors")
+    gs, ge, gl = (t.to(device=dev, dtype=torch.int32).contiguous() for t in (gs, ge, gl))
+    vids, nids = vnmap.tables(dev)
+    cost = torch.empty(Q, G, device=dev, dtype=_f32)
+    _check(lib.fx_vn_match_cost(nx.ptr(xa), nx.ld(xa), Q, n1, n2, nx.ptr(vids), nx.ptr(nids), vnmap.num_actions,
+                                nx.ptr(at), nx.ld(at), rows, nx.ptr(st), nx.ptr(en), nx.ptr(gs), nx.ptr(ge),
+                                nx.ptr(gl), G, int(T), float(pc), float(a2fc), nx.ptr(cost), nx.stream()),
+           "fx_vn_match_cost")
+    return cost
+
+
 # ---------------------------------------------------------------------------
 # L2 normalisation
 # ---------------------------------------------------------------------------

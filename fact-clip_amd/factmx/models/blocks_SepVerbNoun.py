@@ -11,7 +11,10 @@ captured by a model at construction.  Compute runs on the HIP kernels through fa
 videos run one by one and the losses per video, as in the reference (no lockstep batch path).
 With ``FUSED_LOSS`` the class terms of the loss and the prediction of CUDA inputs come straight from
 the class logits (functional.vn_class_loss / vn_eval_pred): ``frame_logp`` / ``seg_logp`` are then
-computed only when something reads them.
+computed only when something reads them.  With ``vn_vloss.FUSED_TABLE`` as well, the matching cost comes
+from the token heads and the segment-level attention (functional.vn_match_cost) and every loss term of
+the video runs from one term table (models/vn_vloss.py); the frame-level ``a2f_attn`` / ``f2a_attn`` are
+gathered from the segment rows only when something reads them.
 """
 import torch
 import torch.nn as nn
@@ -20,6 +23,7 @@ from .. import functional as fxf
 from ..configs.utils import update_from
 from . import basic
 from . import loss
+from . import vn_vloss
 from .basic import time_mask, torch_class_label_to_segment_label
 from .blocks import _frame_pos, _Lazy, _lazy_attr
 from .loss import MatchCriterion
@@ -132,7 +136,14 @@ class FACT(nn.Module):
         mcriterion: MatchCriterion = self.mcriterion
         mcriterion.set_label(label)
         block = self.block_list[-1]
-        match = mcriterion.match(torch.exp(block.action_logp), block.a2f_attn)
+        if vn_vloss.FUSED_TABLE and vn_vloss.supported(self):
+            # segment rows + TDU intervals and the token heads: no frame-level attention, no cost cube
+            match = mcriterion.match(None, block.a2f_seg_attn, tdu=block.tdu, vn=(block._clogits[2], self.vnmap))
+            total = vn_vloss.run(self, mcriterion, match, label)
+            if total is not None:
+                return total
+        else:
+            match = mcriterion.match(torch.exp(block.action_logp), block.a2f_attn)
         self.loss_list = [blk.compute_loss(mcriterion, match) for blk in self.block_list]
         return sum(self.loss_list) / len(self.loss_list)
 
@@ -175,6 +186,9 @@ class Block(nn.Module):
     # side-channel tables nothing on the fused path reads: built on first read
     frame_logp = _lazy_attr("frame_logp")
     seg_logp = _lazy_attr("seg_logp")
+    # frame-level gathers of the segment attention rows (a2f_seg_attn / f2a_seg_attn, (1, S, Q))
+    a2f_attn = _lazy_attr("a2f_attn")
+    f2a_attn = _lazy_attr("f2a_attn")
 
     def __repr__(self):
         return (f"{type(self).__name__}(\n  f:{self.frame_branch},\n  a:{self.action_branch},\n"
@@ -261,6 +275,16 @@ class Block(nn.Module):
         self.action_logp = self.combine_verb_noun_to_action(action_clogit, action=True)
         self.tdu = tdu
 
+    def _save_attn(self, tdu, f2a_seg, a2f_seg):
+        """The cross-attention side channels: the (1, S, Q) segment rows as they are, and the reference's
+        frame-level ``f2a_attn`` (1, Q, T) / ``a2f_attn`` (1, T, Q) gathered on first read."""
+        self.f2a_seg_attn, self.a2f_seg_attn = f2a_seg, a2f_seg
+        if tdu is None:
+            self.f2a_attn = self.a2f_attn = None
+            return
+        self.f2a_attn = _Lazy(lambda: tdu.attn_seg2frame(f2a_seg).transpose(2, 1))
+        self.a2f_attn = _Lazy(lambda: tdu.attn_seg2frame(a2f_seg))
+
     def _token_loss(self, criterion: MatchCriterion, match):
         if self._fused:
             return criterion.vn_token_terms(match, self._clogits[2], self.vnmap)
@@ -298,6 +322,9 @@ class Block(nn.Module):
 
     def eval(self, transcript=None):
         if not self.cfg.FACT.trans:
+            if self._fused and self.a2f_seg_attn is not None:
+                return fxf.vn_eval_pred(self._clogits[2], self._clogits[0], self.a2f_seg_attn, self.vnmap,
+                                        self.cfg.FACT.mwt, seg_id=self.tdu.seg_id32)
             if self._fused:
                 return fxf.vn_eval_pred(self._clogits[2], self._clogits[0], self.a2f_attn, self.vnmap,
                                         self.cfg.FACT.mwt)
@@ -328,8 +355,7 @@ class InputBlockTDU(Block):
         action_feature = self.action_branch(action_feature, seg_feature, pos=seg_pos, query_pos=action_pos)
         action_feature, action_clogit = self.process_feature(action_feature, self.nclass1 + 1, self.nclass2 + 1)
         self._save_logp(frame_clogit, seg_clogit, action_clogit, tdu)
-        self.f2a_attn = None
-        self.a2f_attn = None
+        self._save_attn(None, None, None)
         return frame_feature, action_feature
 
     def compute_loss(self, criterion: MatchCriterion, match=None):
@@ -367,9 +393,8 @@ class UpdateBlockTDU(Block):
         frame_feature, frame_clogit = self.process_feature(frame_feature, self.nclass1, self.nclass2)
         self._save_logp(frame_clogit, seg_clogit, action_clogit, tdu)
         self.f2a_attn_logit = self.f2a_layer.attn_logit.squeeze(0).unsqueeze(0)
-        self.f2a_attn = tdu.attn_seg2frame(self.f2a_layer.attn[0].transpose(2, 1)).transpose(2, 1)
         self.a2f_attn_logit = self.a2f_layer.attn_logit.squeeze(0).unsqueeze(0)
-        self.a2f_attn = tdu.attn_seg2frame(self.a2f_layer.attn[0])
+        self._save_attn(tdu, self.f2a_layer.attn[0].transpose(2, 1), self.a2f_layer.attn[0])
         return frame_feature, action_feature
 
     def compute_loss(self, criterion: MatchCriterion, match=None):

@@ -110,6 +110,7 @@ class MatchCriterion:
                 sw = torch.where(self.transcript == i, torch.full_like(sw, self.cfg.Loss.bgw), sw)
         self.cweight, self.sweight = cw, sw
         self._match_cache = None
+        self._gt_dev = None
 
     @property
     def onehot_class_label(self):
@@ -137,22 +138,51 @@ class MatchCriterion:
         union = torch.minimum(a[:, :, None] + onehot_seg_label[:, None, :], torch.ones((), device=a.device)).sum(0)
         return torch.nan_to_num(overlap / union, nan=0.0)
 
-    def match(self, clogit, a2f_attn):
-        """loss.py:108-153: Hungarian (o2o) / one-to-many / sequential matching."""
-        assert clogit.shape[1] == 1
+    def gt_device(self):
+        """(starts, ends inclusive, actions) int32 device tensors of the label's ground-truth segments,
+        made on first use from ``seg_label`` / ``transcript`` (no host read)."""
+        gt = getattr(self, "_gt_dev", None)
+        if gt is None:
+            G = int(self.transcript.shape[0])
+            sl = self.seg_label.to(torch.int64)
+            cnt = torch.zeros(G, dtype=torch.int64, device=sl.device).index_add_(0, sl, torch.ones_like(sl))
+            ge = torch.cumsum(cnt, 0) - 1
+            gt = self._gt_dev = ((ge - cnt + 1).to(torch.int32), ge.to(torch.int32), self.transcript.to(torch.int32))
+        return gt
+
+    def match(self, clogit, a2f_attn, tdu=None, vn=None):
+        """loss.py:108-153: Hungarian (o2o) / one-to-many / sequential matching.  With ``tdu``,
+        ``a2f_attn`` is the segment-level (1, S, Q) attention of that segmentation.  With
+        ``vn = (action_clogit, vnmap)`` on CUDA tensors the cost comes from the token heads
+        (functional.vn_match_cost: no frames x tokens x segments cube, no frame-level attention) and
+        ``clogit`` is not read; on CPU tensors the call computes what
+        ``match(clogit, tdu.attn_seg2frame(a2f_attn))`` computes."""
         mcfg = self.cfg.Loss
         S = self.onehot_seg_label.shape[-1]
+        fused = vn is not None and vn[0].is_cuda
+        if not fused:
+            assert clogit.shape[1] == 1
         if mcfg.match == "seq":
-            A = clogit.shape[0]
+            A = vn[0].shape[0] if fused else clogit.shape[0]
             assert A >= S, (A, S)
             idx = torch.arange(S, dtype=torch.int64)
             return idx, idx
+        dev = vn[0].device if fused else clogit.device
         with torch.no_grad():
-            cost = torch.zeros(clogit.shape[0], S, device=clogit.device)
-            if mcfg.pc > 0:
-                cost = cost - mcfg.pc * clogit.squeeze(1)[:, self.transcript]
-            if mcfg.a2fc > 0:
-                cost = cost - mcfg.a2fc * self.a2f_soft_iou(a2f_attn, self.onehot_seg_label)
+            if fused:
+                gs, ge, gl = self.gt_device()
+                cost = fxf.vn_match_cost(vn[0], a2f_attn, vn[1], gs, ge, gl, int(self.seg_label.shape[0]),
+                                         mcfg.pc if mcfg.pc > 0 else 0.0, mcfg.a2fc if mcfg.a2fc > 0 else 0.0,
+                                         seg_start=None if tdu is None else tdu.start32,
+                                         seg_end=None if tdu is None else tdu.end32)
+            else:
+                if tdu is not None:
+                    a2f_attn = tdu.attn_seg2frame(a2f_attn)
+                cost = torch.zeros(clogit.shape[0], S, device=dev)
+                if mcfg.pc > 0:
+                    cost = cost - mcfg.pc * clogit.squeeze(1)[:, self.transcript]
+                if mcfg.a2fc > 0:
+                    cost = cost - mcfg.a2fc * self.a2f_soft_iou(a2f_attn, self.onehot_seg_label)
             cost = cost.double().cpu().numpy()
         if mcfg.match == "o2o":
             ai, si = linear_sum_assignment(cost)
@@ -162,7 +192,7 @@ class MatchCriterion:
             raise ValueError(mcfg.match)
         ai = torch.as_tensor(np.asarray(ai), dtype=torch.int64)
         si = torch.as_tensor(np.asarray(si), dtype=torch.int64)
-        self._match_cache = (ai, si, _to_dev(ai, clogit.device), _to_dev(si, clogit.device))
+        self._match_cache = (ai, si, _to_dev(ai, dev), _to_dev(si, dev))
         return ai, si
 
     def _dev_match(self, match, dev):

@@ -12,7 +12,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FACTMX_LIB", os.path.join(_HERE, "_lib", "libfactmx.so"))
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 P = ctypes.c_void_p
 I = ctypes.c_int
@@ -89,7 +89,7 @@ STATUS_TOK_TIMEOUT = 2   # FX_STATUS_TOK_TIMEOUT: a persistent token-kernel barr
 STATUS_X2Y_TIMEOUT = 4   # FX_STATUS_X2Y_TIMEOUT: the one-launch X2Y f2a backward's grid barrier gave up
 LOSS_MAXK = 512        # FX_LOSS_MAXK: matched columns of an attention loss term
 LOSS_NB = 128          # FX_LOSS_NB: row blocks per loss term
-TERM_CLASS, TERM_ATTN, TERM_INFONCE = 0, 1, 2
+TERM_CLASS, TERM_ATTN, TERM_INFONCE, TERM_VNCLASS = 0, 1, 2, 3
 PREC_DEFAULT, PREC_F32, PREC_BF16, PREC_F32S, PREC_F32S2 = -1, 0, 1, 2, 3   # FX_PREC_*: GEMM arithmetic
 
 
@@ -98,7 +98,13 @@ class LossTerm(ctypes.Structure):
                 ("dsc", L), ("y", P), ("rs", P), ("re", P), ("gs", P), ("ge", P), ("gl", P), ("G", I), ("axis", I),
                 ("K", I), ("D", I), ("w", P), ("c_ce", F), ("c_sm", F), ("inv_temp", F), ("pad0", F), ("lse", P),
                 ("lse2", P), ("colz", P), ("emb", P), ("ld_emb", L), ("text", P), ("demb", P), ("ld_demb", L),
-                ("ka", P), ("kgs", P), ("kge", P), ("ksw", P)]
+                ("ka", P), ("kgs", P), ("kge", P), ("ksw", P), ("vn", P), ("vn_host", P)]
+
+
+class VnTerm(ctypes.Structure):
+    """fx_vn_term: the action -> (verb, noun) mapping a TERM_VNCLASS term points to."""
+    _fields_ = [("n1", I), ("n2", I), ("A", I), ("null", I), ("vids", P), ("nids", P), ("voff", P), ("vlist", P),
+                ("noff", P), ("nlist", P)]
 
 
 class VideoAttn(ctypes.Structure):
@@ -106,7 +112,7 @@ class VideoAttn(ctypes.Structure):
                 ("seg_id", P), ("flogit", P), ("ldf", L), ("gs", P), ("ge", P), ("gl", P), ("pred_off", L)]
 
 
-ABI_STRUCTS = (GemmDesc, DecoderParams, MstcnParams, LossTerm, VideoAttn, Mstcn2Params)   # fx_struct_size ids
+ABI_STRUCTS = (GemmDesc, DecoderParams, MstcnParams, LossTerm, VideoAttn, Mstcn2Params, VnTerm)   # fx_struct_size ids
 
 
 # name -> (restype, argtypes); every fx_* symbol declared in include/factmx.h
@@ -161,6 +167,7 @@ SIGNATURES = {
     "fx_vn_loss_fwd": (I, [P, L, I, I, I, P, P, I, I, P, I, P, P, P, F, F, P, P, P, P]),
     "fx_vn_loss_bwd": (I, [P, L, I, I, I, P, P, I, I, P, I, P, P, P, P, P, P, P, P, F, F, P, P, L, P]),
     "fx_vn_eval_pred": (I, [P, L, I, P, L, I, I, I, P, P, I, P, L, P, I, F, P, P, P]),
+    "fx_vn_match_cost": (I, [P, L, I, I, I, P, P, I, P, L, I, P, P, P, P, P, I, I, F, F, P, P]),
     "fx_l2norm_fwd": (I, [P, L, I, I, P, L, P, P]),
     "fx_l2norm_bwd": (I, [P, L, P, P, L, I, I, P, L, P]),
     "fx_relu_bwd": (I, [P, L, P, L, I, I, P, L, P]),

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define FX_ABI_VERSION 24
+#define FX_ABI_VERSION 25
 
 enum {
   FX_OK = 0,
@@ -561,6 +561,30 @@ int fx_vn_eval_pred(const float* action_clogit, long long lda, int Q, const floa
                     float* workspace, int32_t* pred, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Matching cost of one video of the verb / noun model (MatchCriterion.match,
+ * loss.py:108-153, a2f_soft_iou 91-106, token probabilities of
+ * blocks_SepVerbNoun.py:189-224), cost (Q x G) fp32, row-major:
+ *   cost[a, s] = -pc * P[a, gl[s]] - a2fc * overlap[a, s] / union[a, s]
+ *   P[a, y] = exp(lsv[a, vids[y]] + lsn[a, nids[y]]), lsv / lsn the log-softmax
+ *   of token a's n1 + 1 verb / n2 + 1 noun head logits (action_clogit,
+ *   Q x (n1 + n2 + 2)); gl clamped into [0, A).
+ *   overlap[a, s] = token a's frame attention summed over the ground-truth
+ *   segment [gs[s], ge[s]] (inclusive frames; the G segments tile [0, T) in
+ *   ascending order), union = len_s + sum_s' overlap[a, s'] - overlap[a, s]
+ *   (attention <= 1); union == 0 gives 0.  No T x Q x G intermediate.
+ * attn (nattn x Q, ldattn): segment level with seg_start / seg_end (nattn, device
+ * int32, the TDU intervals tiling [0, T) in ascending order): an interval's sum is
+ * sum_j attn[j, a] * |[start_j, end_j] n [gs, ge]| over ascending j, O(S + G) per
+ * token; seg_start == NULL: the rows are frames (nattn == T).
+ * One workgroup per token; no float atomics, fixed-order reductions, bitwise
+ * repeatable; Q == 0 launches nothing; n1 + n2 + 2 <= 2048.
+ * ---------------------------------------------------------------------- */
+int fx_vn_match_cost(const float* action_clogit, long long lda, int Q, int n1, int n2, const int32_t* vids,
+                     const int32_t* nids, int A, const float* attn, long long ldattn, int nattn,
+                     const int32_t* seg_start, const int32_t* seg_end, const int32_t* gs, const int32_t* ge,
+                     const int32_t* gl, int G, int T, float pc, float a2fc, float* cost, void* stream);
+
+/* ------------------------------------------------------------------------
  * F.normalize(dim=-1, eps=1e-12) (blocks.py:174) and its backward.
  * ---------------------------------------------------------------------- */
 int fx_l2norm_fwd(const float* x, long long ldx, int rows, int cols, float* y, long long ldy,
@@ -774,14 +798,31 @@ int fx_attn_loss_bwd(const float* L, long long sr, long long sc, int R, int Q, i
  *   FX_TERM_INFONCE x (R x C) <- emb . text^T * inv_temp (one GEMM), y class per
  *                   frame (-1 = held out), c_ce * (row CE mean + per-class column
  *                   log-softmax mean); backward writes demb.
+ *   FX_TERM_VNCLASS the value and gradient of fx_vn_loss_fwd / fx_vn_loss_bwd on x (R x C,
+ *                   C = n1 + n2 head logits, sc == dsc == 1): c_ce * sum_r CE_r + c_sm * smooth
+ *                   over the factorised action log-probabilities.  vn / vn_host: the
+ *                   mapping (device copy for the kernels, host copy for the entry
+ *                   points' checks).  y (int32): the R hard labels (label A with
+ *                   null: the null column) or, with rs / re, the D frame labels the
+ *                   segment rows [rs[r], re[r]] average over; y == NULL: no CE term.
+ *                   w: A + null weights.  lse: 2 R floats.  One launch covers the
+ *                   table's VNCLASS terms forward (workgroup b of a term takes rows
+ *                   b, b + FX_LOSS_NB, ... in ascending order) and one backward.
  * Scratch per term: lse (R), lse2 (R + K or C), colz (K, or for InfoNCE: C counts + valid
  * frames padded to a multiple of 4, then 4 * FX_LOSS_NB * C per-row-block column partials)
  * floats; InfoNCE colz 16-byte aligned.
  * bwd: gout (nout) upstream gradient of out; every term's dx (and demb) written whole.
  * ---------------------------------------------------------------------- */
-enum { FX_TERM_CLASS = 0, FX_TERM_ATTN = 1, FX_TERM_INFONCE = 2 };
+enum { FX_TERM_CLASS = 0, FX_TERM_ATTN = 1, FX_TERM_INFONCE = 2, FX_TERM_VNCLASS = 3 };
 #define FX_LOSS_NB 128          /* row blocks per term */
 #define FX_LOSS_MAXK 512        /* matched columns of an attention term (one wave each on axis 0) */
+
+/* the action -> (verb, noun) mapping of a VNCLASS term (tables as for fx_vn_loss_*) */
+typedef struct fx_vn_term {
+  int n1, n2, A, null;
+  const int32_t* vids; const int32_t* nids;
+  const int32_t* voff; const int32_t* vlist; const int32_t* noff; const int32_t* nlist;   /* backward only */
+} fx_vn_term;
 
 typedef struct fx_loss_term {
   int kind, slot, R, C;
@@ -799,6 +840,8 @@ typedef struct fx_loss_term {
   float* demb; long long ld_demb;
   const int32_t* ka; const int32_t* kgs; const int32_t* kge;   /* device (K): matched token columns and their */
   const float* ksw;                                            /* ground-truth segments [kgs, kge], weights */
+  const fx_vn_term* vn;        /* VNCLASS: the mapping on the device; NULL for the other kinds */
+  const fx_vn_term* vn_host;   /* VNCLASS: its host copy */
 } fx_loss_term;
 
 long long fx_loss_terms_workspace_floats(int nterms);
