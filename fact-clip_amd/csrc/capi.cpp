@@ -623,6 +623,7 @@ long long fx_struct_size(int which) {
     case 4: return (long long)sizeof(fx_video_attn);
     case 5: return (long long)sizeof(fx_mstcn2_params);
     case 6: return (long long)sizeof(fx_vn_term);
+    case 7: return (long long)sizeof(fx_vn_video);
     default: return -1;
   }
 }

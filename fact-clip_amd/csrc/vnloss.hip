@@ -11,6 +11,8 @@
 //                     workgroup b of a term takes rows b, b + FX_LOSS_NB, ... in ascending order
 //   vn_match_cost   : MatchCriterion.match's cost (loss.py:108-153, soft IoU 91-106) from the token heads
 //                     and interval overlaps of the (segment-level) attention, no T x Q x G cube
+//   *_batch         : vn_match_cost / vn_eval_pred for every video of a batch (fx_vn_video descriptors): the
+//                     same row code as the single-video kernels over a (row, video) grid
 // Layout: one 256-thread workgroup per row (frame, segment or token).
 // Determinism: no float atomics.  Reductions are wave shuffles in a fixed tree plus a fixed-order
 // combine of the 4 wave partials; per-row partial sums are added by one workgroup in a fixed order;
@@ -399,15 +401,12 @@ __global__ __launch_bounds__(VL_THREADS) void vn_terms_bwd_kernel(const fx_loss_
 // ---------------------------------------------------------------- prediction
 // per token q: ws row q = log-softmax of the n1 + 1 / n2 + 1 token heads, then Z_q = sum_a exp(logp[q, a])
 // and is_tok (the null column is not the first maximum over the A + 1 columns)
-__global__ __launch_bounds__(VL_THREADS) void vn_eval_tok_kernel(const float* aclogit, long long lda, int n1, int n2,
-                                                                 const int32_t* vids, const int32_t* nids, int A,
-                                                                 float* ws, int wld) {
-  __shared__ float sh[VL_MAXH];
-  __shared__ float part[4];
-  const int q = blockIdx.x, tid = threadIdx.x;
+__device__ inline void vl_eval_tok_row(const float* arow, int n1, int n2, const int32_t* vids, const int32_t* nids,
+                                       int A, float* wr, float* sh, float* part) {
+  const int tid = threadIdx.x;
   const int m1 = n1 + 1, m2 = n2 + 1, m = m1 + m2;
   float lv, ln;
-  vl_stage_row(aclogit + (long long)q * lda, m1, m2, sh, part, &lv, &ln);
+  vl_stage_row(arow, m1, m2, sh, part, &lv, &ln);
   float z = 0.f, best = -INFINITY;
   for (int c = tid; c < A; c += VL_THREADS) {
     const int v = min(max(vids[c], 0), n1 - 1), k = min(max(nids[c], 0), n2 - 1);
@@ -417,7 +416,6 @@ __global__ __launch_bounds__(VL_THREADS) void vn_eval_tok_kernel(const float* ac
   }
   z = vl_block_sum(z, part);
   best = vl_block_max(best, part);
-  float* wr = ws + (long long)q * wld;
   for (int c = tid; c < m; c += VL_THREADS) wr[c] = sh[c];
   if (tid == 0) {
     wr[m] = z;
@@ -425,24 +423,45 @@ __global__ __launch_bounds__(VL_THREADS) void vn_eval_tok_kernel(const float* ac
   }
 }
 
+__global__ __launch_bounds__(VL_THREADS) void vn_eval_tok_kernel(const float* aclogit, long long lda, int n1, int n2,
+                                                                 const int32_t* vids, const int32_t* nids, int A,
+                                                                 float* ws, int wld) {
+  __shared__ float sh[VL_MAXH];
+  __shared__ float part[4];
+  const int q = blockIdx.x;
+  vl_eval_tok_row(aclogit + (long long)q * lda, n1, n2, vids, nids, A, ws + (long long)q * wld, sh, part);
+}
+
 // per frame t: the first maximum of its attention over the non-null tokens, then the first maximum over a
 // of (1 - w) exp(logp_q[tok, a]) / Z_tok + w exp(logp_f[t, a])  (no non-null token: of exp(logp_f[t, a]))
-__global__ __launch_bounds__(VL_THREADS) void vn_eval_frame_kernel(const float* fclogit, long long ldf, int n1, int n2,
-                                                                   const int32_t* vids, const int32_t* nids, int A,
-                                                                   const float* attn, long long ldattn,
-                                                                   const int32_t* seg_id, int nattn, int Q,
-                                                                   const float* ws, int wld, float w1, float w,
-                                                                   int32_t* pred) {
-  __shared__ float fl[VL_MAXH];
-  __shared__ float tk[VL_MAXH];
-  __shared__ float part[4];
-  __shared__ int parti[4];
-  const int t = blockIdx.x, tid = threadIdx.x;
+struct VnEvalArgs {
+  const float* fclogit;   // (T, n1 + n2) frame heads
+  long long ldf;
+  int n1, n2, A;
+  const int32_t* vids;
+  const int32_t* nids;
+  const float* attn;      // (nattn, Q): frames (seg_id null) or segment rows
+  long long ldattn;
+  const int32_t* seg_id;
+  int nattn, Q;
+  const float* ws;        // (Q, wld): the token stage's rows
+  int wld;
+  float w1, w;
+};
+
+// fl / tk: VL_MAXH floats of LDS each
+__device__ inline void vl_eval_frame_row(const VnEvalArgs& e, int t, int32_t* pred, float* fl, float* tk, float* part,
+                                         int* parti) {
+  const int tid = threadIdx.x;
+  const int n1 = e.n1, n2 = e.n2, A = e.A, Q = e.Q, wld = e.wld;
+  const int32_t *vids = e.vids, *nids = e.nids;
+  const float* ws = e.ws;
+  const float w1 = e.w1, w = e.w;
   const int m1 = n1 + 1, m = n1 + n2 + 2;
   float lv, ln;
-  vl_stage_row(fclogit + (long long)t * ldf, n1, n2, fl, part, &lv, &ln);
-  const int arow = seg_id ? min(max(seg_id[t], 0), nattn - 1) : t;
-  const float* ar = attn + (long long)arow * ldattn;
+  vl_stage_row(e.fclogit + (long long)t * e.ldf, n1, n2, fl, part, &lv, &ln);
+  const int arow = e.seg_id ? min(max(e.seg_id[t], 0), e.nattn - 1) : t;
+  const float* ar = e.attn + (long long)arow * e.ldattn;
   float bv = -INFINITY;
   int bq = 0x7fffffff;
   for (int q = tid; q < Q; q += VL_THREADS) {
@@ -483,6 +502,50 @@ __global__ __launch_bounds__(VL_THREADS) void vn_eval_frame_kernel(const float* 
   if (tid == 0) pred[t] = bi == 0x7fffffff ? 0 : bi;
 }
 
+__global__ __launch_bounds__(VL_THREADS) void vn_eval_frame_kernel(VnEvalArgs e, int32_t* pred) {
+  __shared__ float fl[VL_MAXH];
+  __shared__ float tk[VL_MAXH];
+  __shared__ float part[4];
+  __shared__ int parti[4];
+  vl_eval_frame_row(e, blockIdx.x, pred, fl, tk, part, parti);
+}
+
+// the two stages over every video of a batch: grid (max Q, nvid) / (max T, nvid), a workgroup past its
+// video's rows returns at once.  Token rows of video v start at workspace row sum_{u < v} Q_u
+__device__ inline long long vl_tok_row0(const fx_vn_video* vv, int vi) {
+  long long r = 0;
+  for (int u = 0; u < vi; ++u) r += vv[u].Q;
+  return r;
+}
+
+__global__ __launch_bounds__(VL_THREADS) void vn_eval_tok_batch_kernel(const fx_vn_video* vv, int n1, int n2,
+                                                                       const int32_t* vids, const int32_t* nids, int A,
+                                                                       float* ws, int wld) {
+  __shared__ float sh[VL_MAXH];
+  __shared__ float part[4];
+  const int vi = blockIdx.y, q = blockIdx.x;
+  const fx_vn_video& v = vv[vi];
+  if (q >= v.Q) return;
+  vl_eval_tok_row(v.action_clogit + (long long)q * v.lda, n1, n2, vids, nids, A,
+                  ws + (vl_tok_row0(vv, vi) + q) * wld, sh, part);
+}
+
+__global__ __launch_bounds__(VL_THREADS) void vn_eval_frame_batch_kernel(const fx_vn_video* vv, int n1, int n2,
+                                                                         const int32_t* vids, const int32_t* nids,
+                                                                         int A, const float* ws, int wld, float w1,
+                                                                         float w, int32_t* pred) {
+  __shared__ float fl[VL_MAXH];
+  __shared__ float tk[VL_MAXH];
+  __shared__ float part[4];
+  __shared__ int parti[4];
+  const int vi = blockIdx.y, t = blockIdx.x;
+  const fx_vn_video& v = vv[vi];
+  if (t >= v.T) return;
+  const VnEvalArgs e{v.frame_clogit, v.ldf, n1, n2, A, vids, nids, v.attn, v.ldattn, v.seg_id, v.nattn, v.Q,
+                     ws + vl_tok_row0(vv, vi) * wld, wld, w1, w};
+  vl_eval_frame_row(e, t, pred + v.pred_off, fl, tk, part, parti);
+}
+
 // ---------------------------------------------------------------- matching cost
 struct VnMatchArgs {
   const float* aclogit;   // (Q, n1 + n2 + 2) token heads
@@ -507,14 +570,11 @@ struct VnMatchArgs {
 // bisection: O(S + G) products per token in all); frame-level attention, one wave per ground-truth
 // segment, lanes over its frames, fixed shuffle tree.  col_a = sum_s overlap[a, s] (every thread its
 // segments in ascending order, then the fixed tree).  Pass 2: the writer of each entry turns it into the cost.
-__global__ __launch_bounds__(VL_THREADS) void vn_match_cost_kernel(VnMatchArgs p, float* cost) {
-  __shared__ float sh[VL_MAXH];
-  __shared__ float part[4];
-  const int a = blockIdx.x, tid = threadIdx.x;
+__device__ inline void vl_match_row(const VnMatchArgs& p, int a, float* crow, float* sh, float* part) {
+  const int tid = threadIdx.x;
   const int m1 = p.n1 + 1, m2 = p.n2 + 1;
   float lv, ln;
   vl_stage_row(p.aclogit + (long long)a * p.lda, m1, m2, sh, part, &lv, &ln);
-  float* crow = cost + (long long)a * p.G;
   const float* acol = p.attn + a;
   float colp = 0.f;
   if (p.seg_start) {
@@ -556,6 +616,34 @@ __global__ __launch_bounds__(VL_THREADS) void vn_match_cost_kernel(VnMatchArgs p
     const int v = min(max(p.vids[y], 0), p.n1 - 1), k = min(max(p.nids[y], 0), p.n2 - 1);
     crow[s] = -p.pc * expf(sh[v] + sh[m1 + k]) - p.a2fc * iou;
   }
+}
+
+__global__ __launch_bounds__(VL_THREADS) void vn_match_cost_kernel(VnMatchArgs p, float* cost) {
+  __shared__ float sh[VL_MAXH];
+  __shared__ float part[4];
+  const int a = blockIdx.x;
+  vl_match_row(p, a, cost + (long long)a * p.G, sh, part);
+}
+
+// every video of a batch: grid (max Q, nvid), cost (nvid, Qmax, Gmax); row (v, a) is the single-video row
+// followed by zeros for s >= G_v, a row past its video's tokens all zeros
+__global__ __launch_bounds__(VL_THREADS) void vn_match_cost_batch_kernel(const fx_vn_video* vv, int n1, int n2,
+                                                                         const int32_t* vids, const int32_t* nids,
+                                                                         int A, float pc, float a2fc, int Gmax,
+                                                                         float* cost) {
+  __shared__ float sh[VL_MAXH];
+  __shared__ float part[4];
+  const int vi = blockIdx.y, a = blockIdx.x;
+  const fx_vn_video& v = vv[vi];
+  float* crow = cost + ((long long)vi * gridDim.x + a) * Gmax;
+  int G = 0;
+  if (a < v.Q) {
+    G = v.G;
+    const VnMatchArgs p{v.action_clogit, v.lda, n1, n2, A, vids, nids, v.attn, v.ldattn, v.nattn, v.seg_start,
+                        v.seg_end, v.gs, v.ge, v.gl, v.G, v.T, pc, a2fc};
+    vl_match_row(p, a, crow, sh, part);
+  }
+  for (int s = G + threadIdx.x; s < Gmax; s += VL_THREADS) crow[s] = 0.f;
 }
 
 int vl_check(int n1, int n2, int A, int rows) {
@@ -678,8 +766,8 @@ int fx_vn_eval_pred(const float* action_clogit, long long lda, int Q, const floa
   fx_launch(vn_eval_tok_kernel, dim3(Q), dim3(VL_THREADS), 0, s, action_clogit, lda, n1, n2, vids, nids, A, workspace,
             wld);
   const float w1 = (float)(1.0 - (double)mwt);
-  fx_launch(vn_eval_frame_kernel, dim3(T), dim3(VL_THREADS), 0, s, frame_clogit, ldf, n1, n2, vids, nids, A, attn,
-            ldattn, seg_id, nattn, Q, (const float*)workspace, wld, w1, mwt, pred);
+  const VnEvalArgs e{frame_clogit, ldf, n1, n2, A, vids, nids, attn, ldattn, seg_id, nattn, Q, workspace, wld, w1, mwt};
+  fx_launch(vn_eval_frame_kernel, dim3(T), dim3(VL_THREADS), 0, s, e, pred);
   FX_CHECK_HIP(hipGetLastError());
   return FX_OK;
 }
@@ -700,6 +788,63 @@ int fx_vn_match_cost(const float* action_clogit, long long lda, int Q, int n1, i
   VnMatchArgs p{action_clogit, lda, n1, n2, A, vids, nids, attn, ldattn, nattn, seg_start, seg_end, gs, ge, gl, G, T,
                 pc, a2fc};
   fx_launch(vn_match_cost_kernel, dim3(Q), dim3(VL_THREADS), 0, (hipStream_t)stream, p, cost);
+  FX_CHECK_HIP(hipGetLastError());
+  return FX_OK;
+}
+
+int fx_vn_match_cost_batch(const fx_vn_video* vids_host, const fx_vn_video* vids_dev, int nvid, int n1, int n2,
+                           const int32_t* vids, const int32_t* nids, int A, float pc, float a2fc, int Gmax,
+                           float* cost, void* stream) {
+  FX_REQUIRE(nvid >= 0 && (nvid == 0 || (vids_host && vids_dev)), "vn_match_cost_batch: bad arguments");
+  FX_TRY(vl_check(n1, n2, A, 0));
+  FX_REQUIRE(n1 + n2 + 2 <= VL_MAXH, "vn_match_cost_batch: need n1 + n2 + 2 <= 2048 token head columns");
+  int Qmax = 0;
+  for (int i = 0; i < nvid; ++i) {
+    const fx_vn_video& v = vids_host[i];
+    FX_REQUIRE(v.Q >= 0 && v.G > 0 && v.T > 0 && v.nattn > 0,
+               "vn_match_cost_batch: need ground-truth segments, frames and attention rows");
+    FX_REQUIRE(v.G <= Gmax, "vn_match_cost_batch: a video has more ground-truth segments than Gmax");
+    FX_REQUIRE(v.lda >= n1 + n2 + 2 && v.ldattn >= v.Q, "vn_match_cost_batch: leading dimension shorter than the row");
+    FX_REQUIRE(!v.seg_start == !v.seg_end, "vn_match_cost_batch: segment-level attention needs starts and ends");
+    FX_REQUIRE(v.seg_start ? v.nattn <= v.T : v.nattn == v.T,
+               "vn_match_cost_batch: frame-level attention needs one row per frame, segment-level at most T rows");
+    FX_REQUIRE(v.Q == 0 || (v.action_clogit && v.attn && v.gs && v.ge && v.gl), "vn_match_cost_batch: bad arguments");
+    Qmax = std::max(Qmax, v.Q);
+  }
+  if (Qmax == 0) return FX_OK;
+  FX_REQUIRE(vids && nids && cost && nvid <= 65535, "vn_match_cost_batch: bad arguments");
+  fx_launch(vn_match_cost_batch_kernel, dim3(Qmax, nvid), dim3(VL_THREADS), 0, (hipStream_t)stream, vids_dev, n1, n2,
+            vids, nids, A, pc, a2fc, Gmax, cost);
+  FX_CHECK_HIP(hipGetLastError());
+  return FX_OK;
+}
+
+int fx_vn_eval_pred_batch(const fx_vn_video* vids_host, const fx_vn_video* vids_dev, int nvid, int n1, int n2,
+                          const int32_t* vids, const int32_t* nids, int A, float mwt, float* workspace, int32_t* pred,
+                          void* stream) {
+  FX_REQUIRE(nvid >= 0 && (nvid == 0 || (vids_host && vids_dev)), "vn_eval_pred_batch: bad arguments");
+  FX_TRY(vl_check(n1, n2, A, 0));
+  FX_REQUIRE(n1 + n2 + 2 <= VL_MAXH, "vn_eval_pred_batch: need n1 + n2 + 2 <= 2048 token head columns");
+  int Qmax = 0, Tmax = 0;
+  for (int i = 0; i < nvid; ++i) {
+    const fx_vn_video& v = vids_host[i];
+    FX_REQUIRE(v.T >= 0 && v.Q > 0 && v.lda >= n1 + n2 + 2 && v.ldf >= n1 + n2 && v.ldattn >= v.Q && v.pred_off >= 0,
+               "vn_eval_pred_batch: bad sizes");
+    FX_REQUIRE(v.seg_id ? v.nattn > 0 : v.nattn == v.T,
+               "vn_eval_pred_batch: frame-level attention needs one row per frame");
+    FX_REQUIRE(v.T == 0 || (v.action_clogit && v.frame_clogit && v.attn), "vn_eval_pred_batch: bad arguments");
+    if (v.T > 0) Qmax = std::max(Qmax, v.Q);
+    Tmax = std::max(Tmax, v.T);
+  }
+  if (Tmax == 0) return FX_OK;
+  FX_REQUIRE(vids && nids && workspace && pred && nvid <= 65535, "vn_eval_pred_batch: bad arguments");
+  hipStream_t s = (hipStream_t)stream;
+  const int wld = n1 + n2 + 4;
+  fx_launch(vn_eval_tok_batch_kernel, dim3(Qmax, nvid), dim3(VL_THREADS), 0, s, vids_dev, n1, n2, vids, nids, A,
+            workspace, wld);
+  const float w1 = (float)(1.0 - (double)mwt);
+  fx_launch(vn_eval_frame_batch_kernel, dim3(Tmax, nvid), dim3(VL_THREADS), 0, s, vids_dev, n1, n2, vids, nids, A,
+            (const float*)workspace, wld, w1, mwt, pred);
   FX_CHECK_HIP(hipGetLastError());
   return FX_OK;
 }

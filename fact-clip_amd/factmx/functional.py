@@ -784,6 +784,133 @@ def vn_match_cost(action_clogit, attn, vnmap, gs, ge, gl, T, pc, a2fc, seg_start
     return cost
 
 
+def _vn_attn2d(attn, Q, what):
+    at = attn.detach()
+    if at.dim() == 3:
+        at = at.squeeze(0)
+    if at.dim() == 2 and at.stride(-1) != 1:
+        at = at.contiguous()
+    if Q == 0 or at.dim() != 2 or at.shape[1] != Q or at.shape[0] == 0:
+        raise ValueError(f"{what}: attention {tuple(at.shape)} for {Q} tokens")
+    return at
+
+
+def _vn_video_table(n, dev):
+    """(host struct array, device byte tensor) for n fx_vn_video descriptors."""
+    arr = nx.array_type(nx.VnVideo, n)()
+    return arr, torch.empty(ctypes.sizeof(arr), dtype=torch.uint8, device=dev)
+
+
+def _vn_video_send(arr, devbuf):
+    host = torch.empty(devbuf.shape[0], dtype=torch.uint8, pin_memory=True)
+    ctypes.memmove(host.data_ptr(), ctypes.addressof(arr), devbuf.shape[0])
+    devbuf.copy_(host, non_blocking=True)
+
+
+def vn_match_cost_batch(videos, vnmap, pc, a2fc):
+    """``vn_match_cost`` of every video of a batch in ONE launch (fx_vn_match_cost_batch).  ``videos``: per
+    video a dict with ``action_clogit`` (Q, V + 1 + N + 1), ``attn`` ((T, Q), or the (S, Q) segment rows
+    with ``seg_start`` / ``seg_end`` (S) int32), ``gs`` / ``ge`` / ``gl`` (G) int32 device tensors and
+    ``T``.  Returns the (nvid, Q, Gmax) fp32 device tensor: entry (v, a, s) is ``vn_match_cost``'s for
+    s < G_v and 0 beyond.  Every video is checked as its single-video twin checks it, before the launch."""
+    lib = nx.load()
+    if not videos:
+        raise ValueError("vn_match_cost_batch: no video")
+    rows = []
+    Q = dev = None
+    for i, v in enumerate(videos):
+        xa = _2d(v["action_clogit"].detach())
+        n1, n2, _ = _vn_heads(xa, vnmap, True, f"vn_match_cost_batch (token heads of video {i})")
+        if Q is None:
+            Q, dev = int(xa.shape[0]), xa.device
+        elif int(xa.shape[0]) != Q:
+            raise ValueError(f"vn_match_cost_batch: video {i} has {xa.shape[0]} tokens, video 0 has {Q}")
+        at = _vn_attn2d(v["attn"], Q, f"vn_match_cost_batch (video {i})")
+        T, nat = int(v["T"]), int(at.shape[0])
+        st, en = v.get("seg_start"), v.get("seg_end")
+        if (st is None) != (en is None):
+            raise ValueError("vn_match_cost_batch: seg_start and seg_end go together")
+        if st is None:
+            if nat != T:
+                raise ValueError(f"vn_match_cost_batch: video {i}: {nat} attention rows for {T} frames")
+        else:
+            if st.shape != (nat,) or en.shape != (nat,) or nat > T:
+                raise ValueError(f"vn_match_cost_batch: video {i}: {nat} segment rows need {nat} starts and ends "
+                                 f"within {T} frames")
+            st = st.to(device=dev, dtype=torch.int32).contiguous()
+            en = en.to(device=dev, dtype=torch.int32).contiguous()
+        gs, ge, gl = v["gs"], v["ge"], v["gl"]
+        G = int(gs.shape[0])
+        if G == 0 or gs.shape != (G,) or ge.shape != (G,) or gl.shape != (G,):
+            raise ValueError(f"vn_match_cost_batch: video {i}: gs / ge / gl must be non-empty (G) tensors")
+        gs, ge, gl = (t.to(device=dev, dtype=torch.int32).contiguous() for t in (gs, ge, gl))
+        rows.append((xa, at, T, nat, st, en, gs, ge, gl, G))
+    nvid = len(rows)
+    Gmax = max(r[-1] for r in rows)
+    arr, devbuf = _vn_video_table(nvid, dev)
+    for a, (xa, at, T, nat, st, en, gs, ge, gl, G) in zip(arr, rows):
+        a.Q, a.T, a.G, a.nattn = Q, T, G, nat
+        a.action_clogit, a.lda = xa.data_ptr(), nx.ld(xa)
+        a.attn, a.ldattn = at.data_ptr(), nx.ld(at)
+        a.seg_start, a.seg_end = nx.ptr(st), nx.ptr(en)
+        a.gs, a.ge, a.gl = gs.data_ptr(), ge.data_ptr(), gl.data_ptr()
+    _vn_video_send(arr, devbuf)
+    vids, nids = vnmap.tables(dev)
+    cost = torch.empty(nvid, Q, Gmax, device=dev, dtype=_f32)
+    _check(lib.fx_vn_match_cost_batch(ctypes.addressof(arr), devbuf.data_ptr(), nvid, n1 - 1, n2 - 1, nx.ptr(vids),
+                                      nx.ptr(nids), vnmap.num_actions, float(pc), float(a2fc), Gmax, nx.ptr(cost),
+                                      nx.stream()), "fx_vn_match_cost_batch")
+    return cost
+
+
+def vn_eval_pred_batch(videos, vnmap, mwt):
+    """``vn_eval_pred`` of every video of a batch in two launches (fx_vn_eval_pred_batch).  ``videos``: per
+    video a dict with ``action_clogit`` (Q, V + 1 + N + 1), ``frame_clogit`` (T, V + N), ``attn`` ((T, Q),
+    or the (S, Q) segment rows with ``seg_id`` (T) int32).  Returns the (sum T) int64 predictions on the
+    device, video v's at its frame offset, without a host sync."""
+    lib = nx.load()
+    if not videos:
+        raise ValueError("vn_eval_pred_batch: no video")
+    rows = []
+    dev = None
+    off = qtot = 0
+    for i, v in enumerate(videos):
+        xa, xf = _2d(v["action_clogit"].detach()), _2d(v["frame_clogit"].detach())
+        n1, n2, _ = _vn_heads(xf, vnmap, False, f"vn_eval_pred_batch (frame heads of video {i})")
+        _vn_heads(xa, vnmap, True, f"vn_eval_pred_batch (token heads of video {i})")
+        dev = xf.device if dev is None else dev
+        T, Q = int(xf.shape[0]), int(xa.shape[0])
+        at = _vn_attn2d(v["attn"], Q, f"vn_eval_pred_batch (video {i})")
+        sid = v.get("seg_id")
+        if sid is None:
+            if at.shape[0] != T:
+                raise ValueError(f"vn_eval_pred_batch: video {i}: {at.shape[0]} attention rows for {T} frames")
+        else:
+            if sid.shape != (T,):
+                raise ValueError(f"vn_eval_pred_batch: video {i}: seg_id {tuple(sid.shape)} for {T} frames")
+            sid = sid.to(device=dev, dtype=torch.int32).contiguous()
+        rows.append((xa, xf, at, sid, T, Q, off))
+        off += T
+        qtot += Q
+    nvid = len(rows)
+    arr, devbuf = _vn_video_table(nvid, dev)
+    for a, (xa, xf, at, sid, T, Q, o) in zip(arr, rows):
+        a.Q, a.T, a.nattn = Q, T, int(at.shape[0])
+        a.action_clogit, a.lda = xa.data_ptr(), nx.ld(xa)
+        a.frame_clogit, a.ldf = xf.data_ptr(), nx.ld(xf)
+        a.attn, a.ldattn = at.data_ptr(), nx.ld(at)
+        a.seg_id = nx.ptr(sid)
+        a.pred_off = o
+    _vn_video_send(arr, devbuf)
+    vids, nids = vnmap.tables(dev)
+    pred = torch.empty(off, device=dev, dtype=torch.int32)
+    ws = _ws(lib.fx_vn_workspace_floats(0, qtot, n1, n2), dev)
+    _check(lib.fx_vn_eval_pred_batch(ctypes.addressof(arr), devbuf.data_ptr(), nvid, n1, n2, nx.ptr(vids),
+                                     nx.ptr(nids), vnmap.num_actions, float(mwt), nx.ptr(ws), nx.ptr(pred),
+                                     nx.stream()), "fx_vn_eval_pred_batch")
+    return pred.to(torch.int64)
+
+
 # ---------------------------------------------------------------------------
 # L2 normalisation
 # ---------------------------------------------------------------------------
@@ -1555,12 +1682,10 @@ def segments_from_probs(x2d, col0, ncls):
 _NS_HOST = {}
 
 
-def segments_from_probs_batched(x2d, col0, ncls, f_off, while_waiting=None):
-    """``segments_from_probs`` for the videos stacked in x2d (host frame-row prefix list f_off, ragged
-    lengths allowed), with ONE host read of all segment counts.  Returns (S list, per-video local
-    (seg_id, start, end) views, global (seg_id, start, end) over the stacked frame rows /
-    concatenated segments).  ``while_waiting``: host work that does not need S, run after the counts'
-    copy is enqueued and before the host waits for it (the device is still working up to this block)."""
+def _segments_batched(launch, x2d, f_off, while_waiting):
+    """The shared body of the two batched segmentations: ``launch(nvid, row_off, pred, seg_id, st, en, ns)``
+    enqueues the per-video argmax + boundary scan; then ONE host read of every video's S and the
+    global tables (fx_segments_globalize)."""
     lib = nx.load()
     dev = x2d.device
     nvid = len(f_off) - 1
@@ -1569,8 +1694,7 @@ def segments_from_probs_batched(x2d, col0, ncls, f_off, while_waiting=None):
     buf = torch.empty(4 * n + nvid, device=dev, dtype=torch.int32)
     pred, seg_id, st, en = buf[:n], buf[n:2 * n], buf[2 * n:3 * n], buf[3 * n:4 * n]
     ns = buf[4 * n:]
-    _check(lib.fx_segments_from_probs(nx.ptr(x2d), nx.ld(x2d), col0, ncls, 0, nvid, ro, nx.ptr(pred), nx.ptr(seg_id),
-                                      nx.ptr(st), nx.ptr(en), nx.ptr(ns), nx.stream()), "fx_segments_from_probs")
+    launch(nvid, ro, pred, seg_id, st, en, ns)
     nh = _NS_HOST.get(nvid)
     if nh is None:
         nh = _NS_HOST[nvid] = torch.empty(nvid, dtype=torch.int32, pin_memory=True)
@@ -1589,6 +1713,38 @@ def segments_from_probs_batched(x2d, col0, ncls, f_off, while_waiting=None):
     local = [(seg_id[f_off[v]:f_off[v + 1]], st[f_off[v]:f_off[v] + S[v]], en[f_off[v]:f_off[v] + S[v]])
              for v in range(nvid)]
     return S, local, (gid, gst, gen)
+
+
+def segments_from_probs_batched(x2d, col0, ncls, f_off, while_waiting=None):
+    """``segments_from_probs`` for the videos stacked in x2d (host frame-row prefix list f_off, ragged
+    lengths allowed), with ONE host read of all segment counts.  Returns (S list, per-video local
+    (seg_id, start, end) views, global (seg_id, start, end) over the stacked frame rows /
+    concatenated segments).  ``while_waiting``: host work that does not need S, run after the counts'
+    copy is enqueued and before the host waits for it (the device is still working up to this block)."""
+    lib = nx.load()
+
+    def launch(nvid, ro, pred, seg_id, st, en, ns):
+        _check(lib.fx_segments_from_probs(nx.ptr(x2d), nx.ld(x2d), col0, ncls, 0, nvid, ro, nx.ptr(pred),
+                                          nx.ptr(seg_id), nx.ptr(st), nx.ptr(en), nx.ptr(ns), nx.stream()),
+               "fx_segments_from_probs")
+    return _segments_batched(launch, x2d, f_off, while_waiting)
+
+
+def segments_from_vn_probs_batched(x2d, col0, n1, n2, vnmap, f_off, while_waiting=None):
+    """``segments_from_vn_probs`` for the videos stacked in x2d, as ``segments_from_probs_batched``: one
+    fx_segments_from_vn_probs launch over the row offsets, ONE host read of every video's S, the
+    global tables.  Same return value."""
+    lib = nx.load()
+    vnmap.check_heads(n1, n2)
+    if len(f_off) < 2 or f_off[0] != 0 or any(b <= a for a, b in zip(f_off, f_off[1:])) or f_off[-1] != x2d.shape[0]:
+        raise ValueError(f"segments_from_vn_probs_batched: row offsets {list(f_off)} for {x2d.shape[0]} rows")
+    vids, nids = vnmap.tables(x2d.device)
+
+    def launch(nvid, ro, pred, seg_id, st, en, ns):
+        _check(lib.fx_segments_from_vn_probs(nx.ptr(x2d), nx.ld(x2d), col0, n1, n2, nx.ptr(vids), nx.ptr(nids),
+                                             vnmap.num_actions, 0, nvid, ro, nx.ptr(pred), nx.ptr(seg_id), nx.ptr(st),
+                                             nx.ptr(en), nx.ptr(ns), nx.stream()), "fx_segments_from_vn_probs")
+    return _segments_batched(launch, x2d, f_off, while_waiting)
 
 
 class SegMeanFn(torch.autograd.Function):

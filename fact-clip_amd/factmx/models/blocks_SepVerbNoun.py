@@ -8,13 +8,17 @@ log-probability is ``log_softmax(verb)[VIDS[a]] + log_softmax(noun)[NIDS[a]]``; 
 (verb, noun) tables live in a ``functional.VerbNounMap`` (the reference's module globals ``_VIDS`` /
 ``_NIDS``), installed by ``init_VIDS_NIDS`` / ``set_verb_noun_ids`` / ``load_verb_noun_ids`` and
 captured by a model at construction.  Compute runs on the HIP kernels through factmx.functional;
-videos run one by one and the losses per video, as in the reference (no lockstep batch path).
+videos run one by one and the losses per video, as in the reference, unless ``LOCKSTEP`` is on (below).
 With ``FUSED_LOSS`` the class terms of the loss and the prediction of CUDA inputs come straight from
 the class logits (functional.vn_class_loss / vn_eval_pred): ``frame_logp`` / ``seg_logp`` are then
 computed only when something reads them.  With ``vn_vloss.FUSED_TABLE`` as well, the matching cost comes
 from the token heads and the segment-level attention (functional.vn_match_cost) and every loss term of
 the video runs from one term table (models/vn_vloss.py); the frame-level ``a2f_attn`` / ``f2a_attn`` are
-gathered from the segment rows only when something reads them.
+gathered from the segment rows only when something reads them.  With ``LOCKSTEP`` on top of both, a
+batch of CUDA videos (any lengths, at most blocks.MAX_LOCKSTEP_VIDEOS, no ``cfg.FACT.trans``) runs
+every block over the stacked videos (``forward_batch``), with one matching-cost launch, one term table,
+one prediction pass and one read-back per step (vn_vloss.run_batch); the side-channel attributes then hold
+the last video's views, as in models.blocks.
 """
 import torch
 import torch.nn as nn
@@ -22,10 +26,12 @@ import torch.nn as nn
 from .. import functional as fxf
 from ..configs.utils import update_from
 from . import basic
+from . import blocks
 from . import loss
+from . import vloss
 from . import vn_vloss
 from .basic import time_mask, torch_class_label_to_segment_label
-from .blocks import _frame_pos, _Lazy, _lazy_attr
+from .blocks import _frame_branch_batch, _frame_pos, _Lazy, _lazy_attr, _set_side, _VideoBatch
 from .loss import MatchCriterion
 
 _VNMAP = None     # the installed mapping (reference: _VIDS / _NIDS)
@@ -34,6 +40,11 @@ _VNMAP = None     # the installed mapping (reference: _VIDS / _NIDS)
 # (functional.vn_class_loss / vn_eval_pred: no T x A table of action log-probabilities is built);
 # False: the eager forms on the materialised tables.
 FUSED_LOSS = True
+
+# All videos of a step through every block in one pass (``forward_batch``), one matching-cost launch, one
+# loss term table, one prediction pass and one read-back for the whole batch (vn_vloss.run_batch), when
+# ``_lockstep_ok`` holds; False, or a batch the guard refuses: the videos run one by one.
+LOCKSTEP = False
 
 MAPPING_FILES = ("./data/epic-kitchens/processed/mapping.txt",
                  "./data/epic-kitchens/processed/verb_mapping.txt",
@@ -70,6 +81,21 @@ def init_VIDS_NIDS():
     if _VNMAP is None:
         load_verb_noun_ids(*MAPPING_FILES)
     return _VNMAP
+
+
+def _lockstep_ok(net, seq_list):
+    """The lockstep pass (any video lengths, one video included) needs the fused loss phase with its term
+    table, at most blocks.MAX_LOCKSTEP_VIDEOS videos, no transcript input, CUDA inputs and the fused
+    decoders; the matching reads the last block's token -> segment attention."""
+    if not (FUSED_LOSS and vn_vloss.FUSED_TABLE):
+        return False
+    if not seq_list or len(seq_list) > blocks.MAX_LOCKSTEP_VIDEOS or net.cfg.FACT.trans:
+        return False
+    if any(not s.is_cuda or s.shape[0] < 1 for s in seq_list):
+        return False
+    if net.cfg.Loss.match not in ("o2o", "o2m", "seq") or not hasattr(net.block_list[-1], "a2f_layer"):
+        return False
+    return all(basic._fused_decoder_ok(blk.action_branch) for blk in net.block_list)
 
 
 class FACT(nn.Module):
@@ -147,7 +173,66 @@ class FACT(nn.Module):
         self.loss_list = [blk.compute_loss(mcriterion, match) for blk in self.block_list]
         return sum(self.loss_list) / len(self.loss_list)
 
+    def _forward_batch(self, seq_list, on_a2f=None):
+        """All videos through the blocks in lockstep, as blocks._FACTBase._forward_batch; returns
+        restore(v), which points every side-channel attribute at video v's views.  ``on_a2f``
+        (vn_vloss.BatchMatch) runs when the last block's token logits and token -> segment attention exist."""
+        nvid = len(seq_list)
+        vb = _VideoBatch(nvid, [int(s.shape[0]) for s in seq_list], self.cfg.FACT.ntoken)
+        vb.on_a2f, vb.last = on_a2f, self.block_list[-1]
+        if on_a2f is not None:
+            dev = seq_list[0].device
+            vb.while_waiting = lambda: on_a2f.prepare(dev)
+        frames = []
+        for seq in seq_list:
+            x = seq.unsqueeze(1)
+            if self.cfg.FACT.cmr and self.training:
+                x = self.channel_masking_dropout(x.permute([1, 2, 0])).permute([2, 0, 1])
+            if self.cfg.TM.use and self.training:
+                x = time_mask(x, self.cfg.TM.t, self.cfg.TM.m, self.cfg.TM.p, replace_with_zero=True)
+            frames.append(x.squeeze(1))
+        f2 = torch.cat(frames, 0)
+        fpe = [_frame_pos(self.frame_pe, s.unsqueeze(1)) for s in seq_list]
+        fpos = None if fpe[0] is None else torch.cat([p.squeeze(1) for p in fpe], 0)
+        # one shared gradient buffer for the query table's readers (fxf.PosGradSink: no pairwise adds)
+        apos = fxf.pos_sink(self.action_query.squeeze(1).repeat(nvid, 1))
+        a2 = torch.zeros_like(apos)
+        for blk in self.block_list:
+            f2, a2 = blk.forward_batch(f2, a2, fpos, apos, vb)
+        self._vb = vb
+
+        def restore(v):
+            for blk in self.block_list:
+                _set_side(blk, blk._vrec[v])
+        return restore
+
+    def _forward_lockstep(self, seq_list, label_list, compute_loss):
+        """``forward`` for a batch ``_lockstep_ok`` accepts.  A batch in which a video's match exceeds
+        FX_LOSS_MAXK runs its losses and predictions per video on the lockstep outputs, as
+        blocks._forward_videos does on TableTooLarge."""
+        nvid = len(seq_list)
+        early = None
+        if compute_loss:
+            early = vn_vloss.BatchMatch(self, [blocks._label_to_host(l_) for l_ in label_list])
+        restore = self._forward_batch(seq_list, early)
+        restore(nvid - 1)       # side-channel attributes: the last video's views, as in the reference
+        self.video_segments = [[blk._bt["S"][v] for blk in self.block_list] for v in range(nvid)]
+        try:
+            return vn_vloss.run_batch(self, self._vb, compute_loss, early)
+        except vloss.TableTooLarge:
+            pass
+        save_list, final_loss, preds = [], [], []
+        for v in range(nvid):
+            restore(v)
+            preds.append(self.block_list[-1].eval(None))
+            save_list.append({})
+            if compute_loss:
+                final_loss.append(self._loss_one_video(label_list[v]))
+        return self._read_back(save_list, preds, final_loss, compute_loss)
+
     def forward(self, seq_list, label_list, compute_loss=False):
+        if LOCKSTEP and _lockstep_ok(self, seq_list):
+            return self._forward_lockstep(seq_list, label_list, compute_loss)
         save_list, final_loss, preds = [], [], []
         for seq, label in zip(seq_list, label_list):
             trans = torch_class_label_to_segment_label(label)[0] if self.cfg.FACT.trans else None
@@ -157,6 +242,10 @@ class FACT(nn.Module):
             save_list.append(save_data)
             if compute_loss:
                 final_loss.append(self._loss_one_video(label))
+        return self._read_back(save_list, preds, final_loss, compute_loss)
+
+    @staticmethod
+    def _read_back(save_list, preds, final_loss, compute_loss):
         # one read-back for every video's predictions, loss floats and the kernels' status word
         dev = preds[0].device
         parts = [p.reshape(-1).to(torch.float64) for p in preds]
@@ -263,6 +352,61 @@ class Block(nn.Module):
                                  lin.weight, lin.bias)
         return y.unsqueeze(1)
 
+    def _downsample_batch(self, f2, fpos, vb):
+        """``temporal_downsample`` over the stacked videos: one segmentation launch + ONE host read of every
+        video's S (the first block: the loss phase's label-only host work runs while the host waits),
+        segment means on the global tables, the BiGRU over the ragged segment rows.  Returns the segment
+        record and (seg feature, seg class logits, seg positions)."""
+        n1, n2 = self.nclass1, self.nclass2
+        hook, vb.while_waiting = vb.while_waiting, None
+        S, local, (gid, gst, gen) = fxf.segments_from_vn_probs_batched(f2, f2.shape[1] - n1 - n2, n1, n2, self.vnmap,
+                                                                        vb.f_off, hook)
+        s_off = [0]
+        for n_ in S:
+            s_off.append(s_off[-1] + n_)
+        seg = fxf.SegMeanFn.apply(f2, gid, gst, gen)
+        seg = fxf.gru(self.seg_update, seg, seq_off=s_off, relu=True)     # relu(seg_update(seg))
+        seg = fxf.linear(seg, self.seg_combine.weight, self.seg_combine.bias)
+        seg_out, seg_cl = fxf.process_feature(seg, n1 + n2, class_sep=n1)
+        seg_pos = None
+        if fpos is not None:
+            seg_pos = fpos[torch.div(gst + gen, 2, rounding_mode="floor").to(torch.int64)]
+        return dict(S=S, s_off=s_off, local=local, glob=(gid, gst, gen)), seg_out, seg_cl, seg_pos
+
+    def _save_batch(self, vb, sg, f_cl, seg_cl, a_cl, attn=None):
+        """Per-video side channels of the stacked outputs as views through one split node per tensor
+        (``_vrec``: what ``_save_logp`` / ``_save_attn`` set for one video), and the stacked tensors the
+        loss phase reads (``_bt``)."""
+        Q, S, nvid = vb.Q, sg["S"], vb.nvid
+        fc, ac, sc = vb.frames(f_cl), vb.tokens(a_cl), torch.split(seg_cl, S)
+        alp = vb.tokens(fxf.verb_noun_logp(a_cl, self.vnmap, action=True))
+        tdus = [basic.TemporalDownsampleUpsample(*sg["local"][v]) for v in range(nvid)]
+        bt = dict(f_cl=f_cl, seg_cl=seg_cl, a_cl=a_cl, S=S, s_off=sg["s_off"], local=sg["local"])
+        if attn is not None:
+            f2a_lg, f2a_at, a2f_lg, a2f_at = attn
+            qs = [Q * n_ for n_ in S]
+            fat, aat, flg, alg = (torch.split(t, qs) for t in (f2a_at, a2f_at, f2a_lg, a2f_lg))
+            bt.update(f2a_lg=f2a_lg, a2f_lg=a2f_lg, a2f_at=a2f_at)
+        recs = []
+        for v in range(nvid):
+            fcv, scv, tdu = fc[v].unsqueeze(1), sc[v].unsqueeze(1), tdus[v]
+            rec = dict(_fused=True, _clogits=(fcv, scv, ac[v].unsqueeze(1)), tdu=tdu,
+                       seg_logp=_Lazy(lambda c=scv: self.combine_verb_noun_to_action(c)),
+                       frame_logp=_Lazy(lambda c=fcv: self.combine_verb_noun_to_action(c)),
+                       action_logp=alp[v].unsqueeze(1))
+            if attn is None:
+                rec.update(f2a_seg_attn=None, a2f_seg_attn=None, f2a_attn=None, a2f_attn=None)
+            else:
+                Sv = S[v]
+                f2a_seg, a2f_seg = fat[v].view(1, Q, Sv).transpose(2, 1), aat[v].view(1, Sv, Q)
+                rec.update(f2a_seg_attn=f2a_seg, a2f_seg_attn=a2f_seg,
+                           f2a_attn=_Lazy(lambda t=tdu, a=f2a_seg: t.attn_seg2frame(a).transpose(2, 1)),
+                           a2f_attn=_Lazy(lambda t=tdu, a=a2f_seg: t.attn_seg2frame(a)),
+                           f2a_attn_logit=flg[v].view(1, Q, Sv), a2f_attn_logit=alg[v].view(1, Sv, Q))
+            recs.append(rec)
+        self.__dict__["_vrec"] = recs     # (plain attributes: no nn.Module.__setattr__ walk)
+        self.__dict__["_bt"] = bt
+
     def _save_logp(self, frame_clogit, seg_clogit, action_clogit, tdu):
         self._fused = FUSED_LOSS and frame_clogit.is_cuda
         self._clogits = (frame_clogit, seg_clogit, action_clogit) if self._fused else None
@@ -358,6 +502,19 @@ class InputBlockTDU(Block):
         self._save_attn(None, None, None)
         return frame_feature, action_feature
 
+    def forward_batch(self, f2, a2, fpos, apos, vb):
+        """``forward`` over vb.nvid stacked videos (frames (sum T, C), tokens (nvid * Q, A)): the SCA decoder
+        reads each video's segment rows through the ragged memory offsets."""
+        n1, n2 = self.nclass1, self.nclass2
+        f = _frame_branch_batch(self.frame_branch, f2, vb)
+        f_out, f_cl = fxf.process_feature(f, n1 + n2, class_sep=n1)
+        sg, seg_out, seg_cl, seg_pos = self._downsample_batch(f_out, fpos, vb)
+        a = fxf.decoder(self.action_branch, a2, seg_out, pos=seg_pos, query_pos=apos, nvid=vb.nvid,
+                        mem_off=sg["s_off"])
+        a_out, a_cl = fxf.process_feature(a, n1 + n2 + 2, class_sep=n1 + 1)
+        self._save_batch(vb, sg, f_cl, seg_cl, a_cl)
+        return f_out, a_out
+
     def compute_loss(self, criterion: MatchCriterion, match=None):
         atk_loss = self._token_loss(criterion, match) / 2
         return self._frame_seg_loss(criterion) + atk_loss
@@ -396,6 +553,29 @@ class UpdateBlockTDU(Block):
         self.a2f_attn_logit = self.a2f_layer.attn_logit.squeeze(0).unsqueeze(0)
         self._save_attn(tdu, self.f2a_layer.attn[0].transpose(2, 1), self.a2f_layer.attn[0])
         return frame_feature, action_feature
+
+    def forward_batch(self, f2, a2, fpos, apos, vb):
+        n1, n2 = self.nclass1, self.nclass2
+        sg, seg_out, seg_cl, seg_pos = self._downsample_batch(f2, fpos, vb)
+        s_off = sg["s_off"]
+        f2a, a2f = self.f2a_layer, self.a2f_layer
+        a, f2a_lg, f2a_at = fxf.x2y(f2a, seg_out, a2, seg_pos if f2a.kq_pos else None, apos if f2a.kq_pos else None,
+                                    rows=(s_off, vb.a_off))
+        a = fxf.decoder(self.action_branch, a, None, query_pos=apos, nvid=vb.nvid)
+        a_out, a_cl = fxf.process_feature(a, n1 + n2 + 2, class_sep=n1 + 1)
+        sgf, a2f_lg, a2f_at = fxf.x2y(a2f, a_out, seg_out, apos if a2f.kq_pos else None,
+                                      seg_pos if a2f.kq_pos else None, rows=(vb.a_off, s_off))
+        if vb.on_a2f is not None and vb.last is self:
+            # the loss phase's matching starts here (vn_vloss.BatchMatch): its cost launch and read-back
+            # queue ahead of sf_merge and the frame branch, the host matching overlaps them
+            vb.on_a2f(vb, a_cl, a2f_at, (s_off, sg["local"]))
+        gid, gst, gen = sg["glob"]
+        lin = self.sf_merge[0]
+        f = fxf.SegMergeFn.apply(sgf, f2, gid, gst, gen, lin.weight, lin.bias)
+        f = _frame_branch_batch(self.frame_branch, f, vb)
+        f_out, f_cl = fxf.process_feature(f, n1 + n2, class_sep=n1)
+        self._save_batch(vb, sg, f_cl, seg_cl, a_cl, (f2a_lg, f2a_at, a2f_lg, a2f_at))
+        return f_out, a_out
 
     def compute_loss(self, criterion: MatchCriterion, match=None):
         atk_loss = self._token_loss(criterion, match) / 2

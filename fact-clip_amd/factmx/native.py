@@ -12,7 +12,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FACTMX_LIB", os.path.join(_HERE, "_lib", "libfactmx.so"))
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 P = ctypes.c_void_p
 I = ctypes.c_int
@@ -112,7 +112,15 @@ class VideoAttn(ctypes.Structure):
                 ("seg_id", P), ("flogit", P), ("ldf", L), ("gs", P), ("ge", P), ("gl", P), ("pred_off", L)]
 
 
-ABI_STRUCTS = (GemmDesc, DecoderParams, MstcnParams, LossTerm, VideoAttn, Mstcn2Params, VnTerm)   # fx_struct_size ids
+class VnVideo(ctypes.Structure):
+    """fx_vn_video: one video of fx_vn_match_cost_batch / fx_vn_eval_pred_batch."""
+    _fields_ = [("Q", I), ("T", I), ("G", I), ("nattn", I), ("action_clogit", P), ("lda", L), ("frame_clogit", P),
+                ("ldf", L), ("attn", P), ("ldattn", L), ("seg_id", P), ("seg_start", P), ("seg_end", P), ("gs", P),
+                ("ge", P), ("gl", P), ("pred_off", L)]
+
+
+# fx_struct_size ids
+ABI_STRUCTS = (GemmDesc, DecoderParams, MstcnParams, LossTerm, VideoAttn, Mstcn2Params, VnTerm, VnVideo)
 
 
 # name -> (restype, argtypes); every fx_* symbol declared in include/factmx.h
@@ -168,6 +176,8 @@ SIGNATURES = {
     "fx_vn_loss_bwd": (I, [P, L, I, I, I, P, P, I, I, P, I, P, P, P, P, P, P, P, P, F, F, P, P, L, P]),
     "fx_vn_eval_pred": (I, [P, L, I, P, L, I, I, I, P, P, I, P, L, P, I, F, P, P, P]),
     "fx_vn_match_cost": (I, [P, L, I, I, I, P, P, I, P, L, I, P, P, P, P, P, I, I, F, F, P, P]),
+    "fx_vn_match_cost_batch": (I, [P, P, I, I, I, P, P, I, F, F, I, P, P]),
+    "fx_vn_eval_pred_batch": (I, [P, P, I, I, I, P, P, I, F, P, P, P]),
     "fx_l2norm_fwd": (I, [P, L, I, I, P, L, P, P]),
     "fx_l2norm_bwd": (I, [P, L, P, P, L, I, I, P, L, P]),
     "fx_relu_bwd": (I, [P, L, P, L, I, I, P, L, P]),

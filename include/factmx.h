@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define FX_ABI_VERSION 25
+#define FX_ABI_VERSION 26
 
 enum {
   FX_OK = 0,
@@ -39,7 +39,7 @@ enum {
 int fx_version(void);
 const char* fx_last_error(void);
 /* sizeof of the ABI structs (0 gemm_desc, 1 decoder_params, 2 mstcn_params, 3 loss_term,
- * 4 video_attn, 5 mstcn2_params) so bindings can check their layouts; -1 for an unknown id */
+ * 4 video_attn, 5 mstcn2_params, 6 vn_term, 7 vn_video) so bindings can check their layouts; -1 for an unknown id */
 long long fx_struct_size(int which);
 
 /* ------------------------------------------------------------------------
@@ -583,6 +583,47 @@ int fx_vn_match_cost(const float* action_clogit, long long lda, int Q, int n1, i
                      const int32_t* nids, int A, const float* attn, long long ldattn, int nattn,
                      const int32_t* seg_start, const int32_t* seg_end, const int32_t* gs, const int32_t* ge,
                      const int32_t* gl, int G, int T, float pc, float a2fc, float* cost, void* stream);
+
+/* ------------------------------------------------------------------------
+ * The two entries above for every video of a batch in one pass (the lockstep
+ * step of the verb / noun model).  A video: Q token rows action_clogit
+ * (Q x (n1+n2+2), lda), T frame rows frame_clogit (T x (n1+n2), ldf; prediction
+ * only), its attention attn (nattn x Q, ldattn) -- frame rows (nattn == T,
+ * seg_start == NULL for the cost, seg_id == NULL for the prediction) or segment
+ * rows with the TDU intervals seg_start / seg_end (nattn; the cost) and the
+ * frame -> row table seg_id (T; the prediction) --, the ground-truth segments
+ * gs / ge / gl (G; the cost) and pred_off, the video's first element of pred.
+ * vids_host / vids_dev: the same nvid descriptors on the host (every argument of
+ * every video is checked there before the launch) and on the device.
+ * fx_vn_match_cost_batch: ONE launch over (token, video).  cost (nvid, Qmax,
+ *   Gmax) fp32, Qmax = max Q_v; entry (v, a, s) with a < Q_v, s < G_v is bitwise
+ *   fx_vn_match_cost's (the same row code), every other entry is 0.  nvid == 0 or
+ *   Q == 0 everywhere launches nothing.
+ * fx_vn_eval_pred_batch: the token stage and the frame stage of fx_vn_eval_pred
+ *   once each for all videos (two launches whatever nvid is);
+ *   pred[pred_off_v + t] equals fx_vn_eval_pred's pred[t] of video v.  workspace:
+ *   fx_vn_workspace_floats(0, sum_v Q_v, n1, n2) floats.
+ * Rules as above: n1 + n2 + 2 <= 2048, ids clamped into their group, no float
+ * atomics, fixed-order reductions, bitwise repeatable, LDS only for the staged
+ * rows.
+ * ---------------------------------------------------------------------- */
+typedef struct fx_vn_video {
+  int Q, T, G, nattn;
+  const float* action_clogit; long long lda;
+  const float* frame_clogit; long long ldf;
+  const float* attn; long long ldattn;
+  const int32_t* seg_id;
+  const int32_t* seg_start; const int32_t* seg_end;
+  const int32_t* gs; const int32_t* ge; const int32_t* gl;
+  long long pred_off;
+} fx_vn_video;
+
+int fx_vn_match_cost_batch(const fx_vn_video* vids_host, const fx_vn_video* vids_dev, int nvid, int n1, int n2,
+                           const int32_t* vids, const int32_t* nids, int A, float pc, float a2fc, int Gmax,
+                           float* cost, void* stream);
+int fx_vn_eval_pred_batch(const fx_vn_video* vids_host, const fx_vn_video* vids_dev, int nvid, int n1, int n2,
+                          const int32_t* vids, const int32_t* nids, int A, float mwt, float* workspace,
+                          int32_t* pred, void* stream);
 
 /* ------------------------------------------------------------------------
  * F.normalize(dim=-1, eps=1e-12) (blocks.py:174) and its backward.
