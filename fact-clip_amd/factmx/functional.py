@@ -706,31 +706,71 @@ def vn_class_loss(clogit, vnmap, weight, *, target=None, frame_label=None, seg_s
     return VnClassLossFn.apply(x, vnmap, n1, n2, k, y, st, en, w, float(c_ce), float(c_sm))
 
 
+def _vn_attn2d(attn, Q, what):
+    at = attn.detach()
+    if at.dim() == 3:
+        at = at.squeeze(0)
+    if at.dim() == 2 and at.stride(-1) != 1:
+        at = at.contiguous()
+    if Q == 0 or at.dim() != 2 or at.shape[1] != Q or at.shape[0] == 0:
+        raise ValueError(f"{what}: attention {tuple(at.shape)} for {Q} tokens")
+    return at
+
+
+def _vn_pred_video(what, vnmap, action_clogit, frame_clogit, attn, seg_id=None, dev=None):
+    """One video's arguments of vn_eval_pred / vn_eval_pred_batch, checked and normalised (``dev``: the
+    batch's device, the frame heads' own by default).  Returns (xa, xf, at, sid, T, Q), (n1, n2)."""
+    xa, xf = _2d(action_clogit.detach()), _2d(frame_clogit.detach())
+    n1, n2, _ = _vn_heads(xf, vnmap, False, f"{what} (frame heads)")
+    _vn_heads(xa, vnmap, True, f"{what} (token heads)")
+    T, Q = int(xf.shape[0]), int(xa.shape[0])
+    at = _vn_attn2d(attn, Q, what)
+    sid = None
+    if seg_id is None:
+        if at.shape[0] != T:
+            raise ValueError(f"{what}: {at.shape[0]} attention rows for {T} frames")
+    else:
+        if seg_id.shape != (T,):
+            raise ValueError(f"{what}: seg_id {tuple(seg_id.shape)} for {T} frames")
+        sid = seg_id.to(device=xf.device if dev is None else dev, dtype=torch.int32).contiguous()
+    return (xa, xf, at, sid, T, Q), (n1, n2)
+
+
+def _vn_match_video(what, vnmap, action_clogit, attn, gs, ge, gl, T, seg_start=None, seg_end=None, dev=None):
+    """One video's arguments of vn_match_cost / vn_match_cost_batch, checked and normalised: the token heads
+    against the mapping, the attention rows against ``T`` frames or against their ``seg_start`` /
+    ``seg_end`` intervals, non-empty ground truth, int32 tensors on ``dev`` (the batch's device, the token
+    heads' own by default).  Returns (xa, at, T, attention rows, st, en, gs, ge, gl, G), (n1, n2)."""
+    xa = _2d(action_clogit.detach())
+    n1, n2, _ = _vn_heads(xa, vnmap, True, f"{what} (token heads)")
+    dev = xa.device if dev is None else dev
+    at = _vn_attn2d(attn, int(xa.shape[0]), what)
+    T, rows = int(T), int(at.shape[0])
+    if (seg_start is None) != (seg_end is None):
+        raise ValueError(f"{what}: seg_start and seg_end go together")
+    st = en = None
+    if seg_start is None:
+        if rows != T:
+            raise ValueError(f"{what}: {rows} attention rows for {T} frames")
+    else:
+        if seg_start.shape != (rows,) or seg_end.shape != (rows,) or rows > T:
+            raise ValueError(f"{what}: {rows} segment rows need {rows} starts and ends within {T} frames")
+        st, en = (t.to(device=dev, dtype=torch.int32).contiguous() for t in (seg_start, seg_end))
+    G = int(gs.shape[0])
+    if G == 0 or gs.shape != (G,) or ge.shape != (G,) or gl.shape != (G,):
+        raise ValueError(f"{what}: gs / ge / gl must be non-empty (G) tensors")
+    gs, ge, gl = (t.to(device=dev, dtype=torch.int32).contiguous() for t in (gs, ge, gl))
+    return (xa, at, T, rows, st, en, gs, ge, gl, G), (n1 - 1, n2 - 1)
+
+
 def vn_eval_pred(action_clogit, frame_clogit, attn, vnmap, mwt, seg_id=None):
     """``Block._eval`` of the verb/noun model (blocks_SepVerbNoun.py:323-342) from the class logits:
     token heads (Q, V + 1 + N + 1), frame heads (T, V + N), token -> frame attention (T, Q) (or
     (1, T, Q)), or the segment-level (S, Q) table with ``seg_id`` (T) int32.  Returns the (T) int64
     prediction on the device, without a host sync."""
     lib = nx.load()
-    xa, xf = _2d(action_clogit.detach()), _2d(frame_clogit.detach())
-    n1, n2, _ = _vn_heads(xf, vnmap, False, "vn_eval_pred (frame heads)")
-    _vn_heads(xa, vnmap, True, "vn_eval_pred (token heads)")
-    at = attn.detach()
-    if at.dim() == 3:
-        at = at.squeeze(0)
-    if at.dim() == 2 and at.stride(-1) != 1:
-        at = at.contiguous()
-    T, Q, dev = xf.shape[0], xa.shape[0], xf.device
-    if Q == 0 or at.dim() != 2 or at.shape[1] != Q:
-        raise ValueError(f"vn_eval_pred: attention {tuple(at.shape)} for {Q} tokens")
-    if seg_id is None:
-        if at.shape[0] != T:
-            raise ValueError(f"vn_eval_pred: {at.shape[0]} attention rows for {T} frames")
-        sid = None
-    else:
-        if seg_id.shape != (T,) or at.shape[0] == 0:
-            raise ValueError(f"vn_eval_pred: seg_id {tuple(seg_id.shape)} for {T} frames")
-        sid = seg_id.to(device=dev, dtype=torch.int32).contiguous()
+    (xa, xf, at, sid, T, Q), (n1, n2) = _vn_pred_video("vn_eval_pred", vnmap, action_clogit, frame_clogit, attn, seg_id)
+    dev = xf.device
     vids, nids = vnmap.tables(dev)
     pred = torch.empty(T, device=dev, dtype=torch.int32)
     ws = _ws(lib.fx_vn_workspace_floats(0, Q, n1, n2), dev)
@@ -748,51 +788,16 @@ def vn_match_cost(action_clogit, attn, vnmap, gs, ge, gl, T, pc, a2fc, seg_start
     int32.  ``gs`` / ``ge`` / ``gl`` (G) int32: the ground-truth segments (inclusive frames) and their
     actions.  No frames x tokens x segments intermediate is built."""
     lib = nx.load()
-    xa = _2d(action_clogit.detach())
-    n1, n2, _ = _vn_heads(xa, vnmap, True, "vn_match_cost (token heads)")
-    n1, n2 = n1 - 1, n2 - 1
-    at = attn.detach()
-    if at.dim() == 3:
-        at = at.squeeze(0)
-    if at.dim() == 2 and at.stride(-1) != 1:
-        at = at.contiguous()
+    (xa, at, T, rows, st, en, gs, ge, gl, G), (n1, n2) = _vn_match_video("vn_match_cost", vnmap, action_clogit, attn,
+                                                                         gs, ge, gl, T, seg_start, seg_end)
     Q, dev = xa.shape[0], xa.device
-    if at.dim() != 2 or at.shape[1] != Q or at.shape[0] == 0:
-        raise ValueError(f"vn_match_cost: attention {tuple(at.shape)} for {Q} tokens")
-    if (seg_start is None) != (seg_end is None):
-        raise ValueError("vn_match_cost: seg_start and seg_end go together")
-    rows = int(at.shape[0])
-    if seg_start is None:
-        if rows != T:
-            raise ValueError(f"vn_match_cost: {rows} attention rows for {T} frames")
-        st = en = None
-    else:
-        if seg_start.shape != (rows,) or seg_end.shape != (rows,) or rows > T:
-            raise ValueError(f"vn_match_cost: {rows} segment rows need {rows} starts and ends within {T} frames")
-        st = seg_start.to(device=dev, dtype=torch.int32).contiguous()
-        en = seg_end.to(device=dev, dtype=torch.int32).contiguous()
-    G = int(gs.shape[0])
-    if G == 0 or gs.shape != (G,) or ge.shape != (G,) or gl.shape != (G,):
-        raise ValueError("vn_match_cost: gs / ge / gl must be non-empty (G) tensors")
-    gs, ge, gl = (t.to(device=dev, dtype=torch.int32).contiguous() for t in (gs, ge, gl))
     vids, nids = vnmap.tables(dev)
     cost = torch.empty(Q, G, device=dev, dtype=_f32)
     _check(lib.fx_vn_match_cost(nx.ptr(xa), nx.ld(xa), Q, n1, n2, nx.ptr(vids), nx.ptr(nids), vnmap.num_actions,
                                 nx.ptr(at), nx.ld(at), rows, nx.ptr(st), nx.ptr(en), nx.ptr(gs), nx.ptr(ge),
-                                nx.ptr(gl), G, int(T), float(pc), float(a2fc), nx.ptr(cost), nx.stream()),
+                                nx.ptr(gl), G, T, float(pc), float(a2fc), nx.ptr(cost), nx.stream()),
            "fx_vn_match_cost")
     return cost
-
-
-def _vn_attn2d(attn, Q, what):
-    at = attn.detach()
-    if at.dim() == 3:
-        at = at.squeeze(0)
-    if at.dim() == 2 and at.stride(-1) != 1:
-        at = at.contiguous()
-    if Q == 0 or at.dim() != 2 or at.shape[1] != Q or at.shape[0] == 0:
-        raise ValueError(f"{what}: attention {tuple(at.shape)} for {Q} tokens")
-    return at
 
 
 def _vn_video_table(n, dev):
@@ -812,39 +817,22 @@ def vn_match_cost_batch(videos, vnmap, pc, a2fc):
     video a dict with ``action_clogit`` (Q, V + 1 + N + 1), ``attn`` ((T, Q), or the (S, Q) segment rows
     with ``seg_start`` / ``seg_end`` (S) int32), ``gs`` / ``ge`` / ``gl`` (G) int32 device tensors and
     ``T``.  Returns the (nvid, Q, Gmax) fp32 device tensor: entry (v, a, s) is ``vn_match_cost``'s for
-    s < G_v and 0 beyond.  Every video is checked as its single-video twin checks it, before the launch."""
+    s < G_v and 0 beyond.  Every video is checked by the function its single-video twin uses, before the
+    launch."""
     lib = nx.load()
     if not videos:
         raise ValueError("vn_match_cost_batch: no video")
     rows = []
     Q = dev = None
     for i, v in enumerate(videos):
-        xa = _2d(v["action_clogit"].detach())
-        n1, n2, _ = _vn_heads(xa, vnmap, True, f"vn_match_cost_batch (token heads of video {i})")
+        row, (n1, n2) = _vn_match_video(f"vn_match_cost_batch: video {i}", vnmap, v["action_clogit"], v["attn"],
+                                        v["gs"], v["ge"], v["gl"], v["T"], v.get("seg_start"), v.get("seg_end"), dev)
+        xa = row[0]
         if Q is None:
             Q, dev = int(xa.shape[0]), xa.device
         elif int(xa.shape[0]) != Q:
             raise ValueError(f"vn_match_cost_batch: video {i} has {xa.shape[0]} tokens, video 0 has {Q}")
-        at = _vn_attn2d(v["attn"], Q, f"vn_match_cost_batch (video {i})")
-        T, nat = int(v["T"]), int(at.shape[0])
-        st, en = v.get("seg_start"), v.get("seg_end")
-        if (st is None) != (en is None):
-            raise ValueError("vn_match_cost_batch: seg_start and seg_end go together")
-        if st is None:
-            if nat != T:
-                raise ValueError(f"vn_match_cost_batch: video {i}: {nat} attention rows for {T} frames")
-        else:
-            if st.shape != (nat,) or en.shape != (nat,) or nat > T:
-                raise ValueError(f"vn_match_cost_batch: video {i}: {nat} segment rows need {nat} starts and ends "
-                                 f"within {T} frames")
-            st = st.to(device=dev, dtype=torch.int32).contiguous()
-            en = en.to(device=dev, dtype=torch.int32).contiguous()
-        gs, ge, gl = v["gs"], v["ge"], v["gl"]
-        G = int(gs.shape[0])
-        if G == 0 or gs.shape != (G,) or ge.shape != (G,) or gl.shape != (G,):
-            raise ValueError(f"vn_match_cost_batch: video {i}: gs / ge / gl must be non-empty (G) tensors")
-        gs, ge, gl = (t.to(device=dev, dtype=torch.int32).contiguous() for t in (gs, ge, gl))
-        rows.append((xa, at, T, nat, st, en, gs, ge, gl, G))
+        rows.append(row)
     nvid = len(rows)
     Gmax = max(r[-1] for r in rows)
     arr, devbuf = _vn_video_table(nvid, dev)
@@ -857,7 +845,7 @@ def vn_match_cost_batch(videos, vnmap, pc, a2fc):
     _vn_video_send(arr, devbuf)
     vids, nids = vnmap.tables(dev)
     cost = torch.empty(nvid, Q, Gmax, device=dev, dtype=_f32)
-    _check(lib.fx_vn_match_cost_batch(ctypes.addressof(arr), devbuf.data_ptr(), nvid, n1 - 1, n2 - 1, nx.ptr(vids),
+    _check(lib.fx_vn_match_cost_batch(ctypes.addressof(arr), devbuf.data_ptr(), nvid, n1, n2, nx.ptr(vids),
                                       nx.ptr(nids), vnmap.num_actions, float(pc), float(a2fc), Gmax, nx.ptr(cost),
                                       nx.stream()), "fx_vn_match_cost_batch")
     return cost
@@ -875,23 +863,12 @@ def vn_eval_pred_batch(videos, vnmap, mwt):
     dev = None
     off = qtot = 0
     for i, v in enumerate(videos):
-        xa, xf = _2d(v["action_clogit"].detach()), _2d(v["frame_clogit"].detach())
-        n1, n2, _ = _vn_heads(xf, vnmap, False, f"vn_eval_pred_batch (frame heads of video {i})")
-        _vn_heads(xa, vnmap, True, f"vn_eval_pred_batch (token heads of video {i})")
-        dev = xf.device if dev is None else dev
-        T, Q = int(xf.shape[0]), int(xa.shape[0])
-        at = _vn_attn2d(v["attn"], Q, f"vn_eval_pred_batch (video {i})")
-        sid = v.get("seg_id")
-        if sid is None:
-            if at.shape[0] != T:
-                raise ValueError(f"vn_eval_pred_batch: video {i}: {at.shape[0]} attention rows for {T} frames")
-        else:
-            if sid.shape != (T,):
-                raise ValueError(f"vn_eval_pred_batch: video {i}: seg_id {tuple(sid.shape)} for {T} frames")
-            sid = sid.to(device=dev, dtype=torch.int32).contiguous()
-        rows.append((xa, xf, at, sid, T, Q, off))
-        off += T
-        qtot += Q
+        row, (n1, n2) = _vn_pred_video(f"vn_eval_pred_batch: video {i}", vnmap, v["action_clogit"], v["frame_clogit"],
+                                       v["attn"], v.get("seg_id"), dev)
+        dev = row[1].device if dev is None else dev
+        rows.append(row + (off,))
+        off += row[4]
+        qtot += row[5]
     nvid = len(rows)
     arr, devbuf = _vn_video_table(nvid, dev)
     for a, (xa, xf, at, sid, T, Q, o) in zip(arr, rows):

@@ -27,46 +27,7 @@ from scipy.optimize import linear_sum_assignment
 from .. import functional as fxf
 from .. import native as nx
 from .loss import one_to_many_match
-
-
-class _Pack:
-    """Host tables and ABI structs laid out in one buffer: allocated on the device first (so the
-    structs can hold device addresses), then filled on the host and sent by ONE non-blocking copy
-    from pinned memory."""
-
-    def __init__(self):
-        self.items = []
-        self.size = 0
-
-    def _reserve(self, nbytes):
-        off = (self.size + 15) & ~15
-        self.size = off + max(int(nbytes), 4)
-        return off
-
-    def array(self, a, dtype):
-        a = np.ascontiguousarray(a, dtype=dtype).reshape(-1)
-        off = self._reserve(a.nbytes)
-        self.items.append((off, a))
-        return off
-
-    def structs(self, ctype, n):
-        arr = (ctype * n)()
-        off = self._reserve(ctypes.sizeof(arr))
-        self.items.append((off, arr))
-        return off, arr
-
-    def alloc(self, dev):
-        self.dev = torch.empty(self.size, dtype=torch.uint8, device=dev)
-        self.base = self.dev.data_ptr()
-        return self.base
-
-    def send(self):
-        host = torch.empty(self.size, dtype=torch.uint8, pin_memory=True)
-        hv = host.numpy()
-        for off, a in self.items:
-            b = np.frombuffer(a, dtype=np.uint8) if isinstance(a, ctypes.Array) else a.view(np.uint8)
-            hv[off:off + b.size] = b
-        self.dev.copy_(host, non_blocking=True)
+from .termtable import TermTable, _LossFn, _Pack, _contig_strides  # noqa: F401  (re-exported: tests, tools)
 
 
 def gt_segments(lab):
@@ -243,50 +204,6 @@ def resolve_pending():
     fxf.resolve_backward_status()
 
 
-class _LossFn(torch.autograd.Function):
-    """(out, loss) = fx_loss_terms_fwd(term table): out = [batch loss, per video (loss, fact, contrastive,
-    per-block)], loss = out[0] as its own 0-dim output (the step's loss.backward() then enters this node
-    directly: no select node, whose backward would zero-fill an nout vector and copy the scalar into it);
-    backward writes every input's gradient whole."""
-
-    @staticmethod
-    def forward(ctx, plan, *inputs):
-        lib = nx.load()
-        dev = inputs[0].device
-        out = torch.empty(plan["nout"], device=dev, dtype=torch.float32)
-        nx.check(lib.fx_loss_terms_fwd(ctypes.addressof(plan["terms_host"]), plan["terms_dev"], plan["nterms"],
-                                       plan["coef_dev"], plan["nout"], nx.ptr(out), nx.ptr(plan["ws"]), nx.stream()),
-                 "fx_loss_terms_fwd")
-        loss = out[0].clone()
-        ctx.plan = plan
-        ctx.set_materialize_grads(False)
-        return out, loss
-
-    @staticmethod
-    def backward(ctx, gout, gloss):
-        plan = ctx.plan
-        lib = nx.load()
-        nout = plan["nout"]
-        gflat, goff, shapes = plan["grads"]
-        if gout is None and gloss is None:
-            return (None,) + tuple(None for _ in shapes)
-        if gout is None:           # only the batch loss was differentiated: row 0 of the coefficients alone
-            gout, nout = gloss.reshape(1).contiguous(), 1
-        else:
-            gout = gout.contiguous()
-            if gloss is not None:
-                gout = gout.clone()
-                gout[0] += gloss
-        nx.check(lib.fx_loss_terms_bwd(ctypes.addressof(plan["terms_host"]), plan["terms_dev"], plan["nterms"],
-                                       plan["coef_dev"], nout, nx.ptr(gout), nx.ptr(plan["ws"]), nx.stream()),
-                 "fx_loss_terms_bwd")
-        rb = plan.get("readback")
-        if rb is not None and not rb.done:       # the step's read-back resolves when the backward pass ends
-            torch.autograd.Variable._execution_engine.queue_callback(rb.resolve)
-        # every input's gradient: its slice of the flat buffer, laid out as the input (contiguous)
-        return (None,) + tuple(gflat.as_strided(shp, st, o) for o, (shp, st) in zip(goff, shapes))
-
-
 def _stage2_labels(net, labs, G):
     """Stage 2's tables that depend on the labels only (EarlyMatch.prepare): the holdout remap and the
     per-video InfoNCE targets (blocks.py:677-747), and the term table's host arrays -- token targets and
@@ -342,14 +259,6 @@ def _stage2_labels(net, labs, G):
     ycon_off = [pk2.array(y, np.int32) if y is not None and con_on[v] else None for v, y in enumerate(y_con)]
     return dict(use_clip=use_clip, con_on=con_on, y_con=y_con, text_seen=text_seen, pk2=pk2, tgt_off=tgt_off,
                 tgt_arr=tgt_arr, kcap=kcap, sw_arr=sw_arr, sw_list=sw_list, ycon_off=ycon_off)
-
-
-def _contig_strides(shape):
-    st, acc = [], 1
-    for n in reversed(tuple(shape)):
-        st.append(acc)
-        acc *= int(n)
-    return tuple(reversed(st))
 
 
 _PINNED = {}
@@ -551,40 +460,11 @@ def run(net, vb, compute_loss, early=None):
                               nx.stream()), "fx_eval_pred")
 
     _stamp("eval_pred")
-    _stamp("pk2_arrays")
-    # every differentiated input of the term table, its gradient a view of ONE flat allocation
-    inputs, gidx = [], {}
-
-    def want(t):
-        if id(t) not in gidx:
-            gidx[id(t)] = len(inputs)
-            inputs.append(t)
-    for blk in blocks:
-        bt = blk._bt
-        for key in ("f_cl", "a_cl", "seg_cl", "f2a_lg", "a2f_lg"):
-            if key in bt and not (key.endswith("_lg") and isinstance(blk, InputBlock)):
-                want(bt[key])
+    # every differentiated input of the term table, its gradient a view of the table's ONE flat allocation
+    inputs = [blk._bt[key] for blk in blocks for key in ("f_cl", "a_cl", "seg_cl", "f2a_lg", "a2f_lg")
+              if key in blk._bt and not (key.endswith("_lg") and isinstance(blk, InputBlock))]
     if any(con_on):
-        want(proj)
-    sizes = [(t.numel() + 63) & ~63 for t in inputs]      # 256-byte aligned slices
-    gflat = torch.empty(sum(sizes), device=dev, dtype=torch.float32)
-    goff, o_ = [], 0
-    for n_ in sizes:
-        goff.append(o_)
-        o_ += n_
-    gb = gflat.data_ptr()
-
-    class _G:       # an input's gradient slice by address only; the tensors are made in the backward
-        __slots__ = ("p",)
-
-        def __init__(self, p):
-            self.p = p
-
-        def data_ptr(self):
-            return self.p
-
-    def grad_of(t):
-        return _G(gb + 4 * goff[gidx[id(t)]])
+        inputs.append(proj)
 
     # The term table in ONE pass straight into the ABI structs (their count is known from the block types:
     # frame CE + token CE per block and video, + the segment CE for a TDU block, + the f2a / a2f cross-
@@ -593,25 +473,16 @@ def run(net, vb, compute_loss, early=None):
     nper = [2 if isinstance(blk, InputBlock) else 5 if isinstance(blk, UpdateBlockTDU) else 4 for blk in blocks]
     nterms = nvid * sum(nper) + sum(1 for c in con_on if c)
     per = 3 + nb
-    nout = 1 + nvid * per
-    coef_off = pk2.array(np.zeros((nout, nterms), dtype=np.float32), np.float32)
-    coef = pk2.items[-1][1].reshape(nout, nterms)          # (the buffer pk2 sends)
-    t_off, terms = pk2.structs(nx.LossTerm, nterms)
-    base2 = pk2.alloc(dev)
+    tt = TermTable(pk2, dev, inputs, np.zeros((1 + nvid * per, nterms), dtype=np.float32))
+    coef, base2, add = tt.coef, tt.base, tt.add
     fw, cwt = float(getattr(cfg.CLIP, "fact_loss_weight", 1.0)), float(getattr(cfg.CLIP, "contrastive_weight", 0.0))
-    tok_terms, attn_terms = [], []     # (term index, video): fields set after the matching
-    slots = []                         # scratch sizes (lse, lse2, colz) per term
+    tok_terms, attn_terms = [], []     # (term, video): fields set after the matching
     # coefficient matrix: out = [batch loss, per video (loss, fact, contrastive, block values...)]
     lw_blk = [fw / nb if con_on[v] else 1.0 / nb for v in range(nvid)]
-    nxt = [0]
 
-    def term(k, v, kind, R, Cc, x, sr, sc, dx, dsr, dsc, c_ce, c_sm, n_lse, n_lse2, n_colz):
-        i = nxt[0]
-        nxt[0] = i + 1
-        t = terms[i]
-        t.slot, t.kind, t.R, t.C, t.x, t.sr, t.sc = i, kind, R, Cc, x, sr, sc
-        t.dx, t.dsr, t.dsc, t.c_ce, t.c_sm = dx, dsr, dsc, c_ce, c_sm
-        slots.append((n_lse, n_lse2, n_colz))
+    def term(k, v, kind, R, Cc, x, sr, sc, g, goff, c_ce, c_sm, kcap=0, ncolz=0):
+        t = add(kind, R, Cc, x, sr, sc, g, goff, sr, sc, c_ce, c_sm, kcap, ncolz)
+        i = t.slot
         o = 1 + v * per
         if k >= 0:
             coef[o + 3 + k, i] = 1.0
@@ -622,7 +493,7 @@ def run(net, vb, compute_loss, early=None):
             lw = cwt
         coef[o, i] = lw
         coef[0, i] = lw / nvid
-        return i, t
+        return t
 
     cw_p = base + cw_off
     for k, blk in enumerate(blocks):
@@ -630,27 +501,24 @@ def run(net, vb, compute_loss, early=None):
         is_tdu = isinstance(blk, UpdateBlockTDU)
         f_cl, a_cl = bt["f_cl"], bt["a_cl"]
         pf, pa = f_cl.data_ptr(), a_cl.data_ptr()
-        gf, ga = grad_of(f_cl).data_ptr(), grad_of(a_cl).data_ptr()
         fce = 0.5 if is_tdu else 1.0
         if not isinstance(blk, InputBlock):
             f2a, a2f = bt["f2a_lg"], bt["a2f_lg"]
             pfa, paf = f2a.data_ptr(), a2f.data_ptr()
-            gfa, gaf = grad_of(f2a).data_ptr(), grad_of(a2f).data_ptr()
             if is_tdu:
                 seg_cl = bt["seg_cl"]
-                psg, gsg = seg_cl.data_ptr(), grad_of(seg_cl).data_ptr()
+                psg = seg_cl.data_ptr()
         for v in range(nvid):
             gs, ge, gl = gt_off[v]
             T = Ts[v]
             # frame CE (+ smooth) on the block's frame logits
-            _, t = term(k, v, nx.TERM_CLASS, T, C, pf + 4 * fo[v] * C, C, 1, gf + 4 * fo[v] * C, C, 1, fce / T,
-                        (sw_coef / ((T - 1) * C) if sw_coef and T > 1 else 0.0), T, 0, 0)
+            t = term(k, v, nx.TERM_CLASS, T, C, pf + 4 * fo[v] * C, C, 1, f_cl, fo[v] * C, fce / T,
+                     (sw_coef / ((T - 1) * C) if sw_coef and T > 1 else 0.0))
             t.y, t.w = base + lab_off[v], cw_p
             # token CE (c_ce = 1 / the targets' class-weight sum, after the matching)
-            i, t = term(k, v, nx.TERM_CLASS, Q, C1, pa + 4 * v * Q * C1, C1, 1, ga + 4 * v * Q * C1, C1, 1, 0.0, 0.0,
-                        Q, 0, 0)
+            t = term(k, v, nx.TERM_CLASS, Q, C1, pa + 4 * v * Q * C1, C1, 1, a_cl, v * Q * C1, 0.0, 0.0)
             t.y, t.w = base2 + tgt_off[v], cw_p
-            tok_terms.append((i, v))
+            tok_terms.append((t, v))
             if isinstance(blk, InputBlock):
                 continue
             ka_o, kgs_o, kge_o, ksw_o = sw_list[v]
@@ -658,8 +526,7 @@ def run(net, vb, compute_loss, early=None):
             if is_tdu:
                 Sv, s0 = bt["S"][v], bt["s_off"][v]
                 rs, re = bt["local"][v][1].data_ptr(), bt["local"][v][2].data_ptr()
-                _, t = term(k, v, nx.TERM_CLASS, Sv, C, psg + 4 * s0 * C, C, 1, gsg + 4 * s0 * C, C, 1, 0.5 / Sv, 0.0,
-                            Sv, 0, 0)
+                t = term(k, v, nx.TERM_CLASS, Sv, C, psg + 4 * s0 * C, C, 1, seg_cl, s0 * C, 0.5 / Sv, 0.0)
                 t.rs, t.re, t.gs, t.ge, t.gl, t.G, t.w = rs, re, base + gs, base + ge, base + gl, G[v], cw_p
                 R, off, c_xe, c_sm = Sv, Q * s0, 1.0 / Sv, 0.0
             else:
@@ -667,12 +534,11 @@ def run(net, vb, compute_loss, early=None):
                 R, off = T, Q * fo[v]
                 c_xe, c_sm = 1.0 / T, (sw_coef / ((T - 1) * Q) if sw_coef and T > 1 else 0.0)
             # f2a logits (Q, R) read as (R, Q): log_softmax over rows per matched column (dim=1)
-            for x, dx, sr, sc, axis in ((pfa, gfa, 1, R, 0), (paf, gaf, Q, 1, 1)):
-                i, t = term(k, v, nx.TERM_ATTN, R, Q, x + 4 * off, sr, sc, dx + 4 * off, sr, sc, c_xe, c_sm,
-                            R, R + Kc, Kc)
+            for x, g, sr, sc, axis in ((pfa, f2a, 1, R, 0), (paf, a2f, Q, 1, 1)):
+                t = term(k, v, nx.TERM_ATTN, R, Q, x + 4 * off, sr, sc, g, off, c_xe, c_sm, Kc)
                 t.rs, t.re, t.axis = rs, re, axis
                 t.ka, t.kgs, t.kge, t.ksw = base2 + ka_o, base2 + kgs_o, base2 + kge_o, base2 + ksw_o
-                attn_terms.append((i, v))
+                attn_terms.append((t, v))
     _stamp("specs")
     sims = None
     if any(con_on):
@@ -680,38 +546,22 @@ def run(net, vb, compute_loss, early=None):
         Dc = text_seen.shape[1]
         sims = torch.empty(2, fo[-1], Cs, device=dev)
         ncolz = ((Cs + 4) & ~3) + 4 * nx.LOSS_NB * Cs
-        gp = grad_of(proj)
         if not all(con_on):     # (videos without a contrastive target leave their projection rows at zero)
-            i_ = gidx[id(proj)]
-            gflat.narrow(0, goff[i_], proj.numel()).zero_()
-        p0, p1, pe, pg = sims[0].data_ptr(), sims[1].data_ptr(), proj.data_ptr(), gp.data_ptr()
+            tt.grad_slice(proj).zero_()
+        p0, p1, pe, pg = sims[0].data_ptr(), sims[1].data_ptr(), proj.data_ptr(), tt.grad_ptr(proj)
         inv_temp = 1.0 / float(cfg.CLIP.temp)
         for v in range(nvid):
             if not con_on[v]:
                 continue
             T = Ts[v]
-            _, t = term(-1, v, nx.TERM_INFONCE, T, Cs, p0 + 4 * fo[v] * Cs, Cs, 1, p1 + 4 * fo[v] * Cs, Cs, 1, 0.5, 0.0,
-                        T, Cs, ncolz)
+            # (its dx is the second similarity table, not an input's gradient: the projection's is demb)
+            t = term(-1, v, nx.TERM_INFONCE, T, Cs, p0 + 4 * fo[v] * Cs, Cs, 1, None, 0, 0.5, 0.0, 0, ncolz)
+            t.dx = p1 + 4 * fo[v] * Cs
             t.y, t.emb, t.ld_emb, t.text, t.D = base2 + ycon_off[v], pe + 4 * fo[v] * Dc, Dc, text_seen.data_ptr(), Dc
             t.inv_temp, t.demb, t.ld_demb = inv_temp, pg + 4 * fo[v] * Dc, Dc
-    assert nxt[0] == nterms, (nxt[0], nterms)
     _stamp("infonce")
-    _stamp("coef")
-    # per-term scratch: lse, lse2, colz slots (16-byte aligned)
-    offs, sc_ = [], 0
-    for sz in slots:
-        o3 = []
-        for n in sz:
-            o3.append(sc_)
-            sc_ += (max(n, 1) + 3) & ~3
-        offs.append(o3)
-    scr = torch.empty(max(sc_, 1), device=dev, dtype=torch.float32)
-    sbase = scr.data_ptr()
-    for i, o3 in enumerate(offs):
-        t = terms[i]
-        t.lse, t.lse2, t.colz = sbase + 4 * o3[0], sbase + 4 * o3[1], sbase + 4 * o3[2]
+    tt.lay_out()
     _stamp("structs")
-    ws = torch.empty(max(lib.fx_loss_terms_workspace_floats(nterms), 1), device=dev, dtype=torch.float32)
 
     # ------------------------------------------------------------------ the matching (waits for the costs)
     matches = early.matches(Q)
@@ -736,17 +586,14 @@ def run(net, vb, compute_loss, early=None):
         kgs[:K] = gts[v][0][si]
         kge[:K] = gts[v][1][si]
         ksw[:K] = swn if len(swn) == K else swn[0]
-    for i, v in tok_terms:
-        terms[i].c_ce = 1.0 / ksum[v]
-    for i, v in attn_terms:
-        terms[i].K = len(matches[v][0])
+    for t, v in tok_terms:
+        t.c_ce = 1.0 / ksum[v]
+    for t, v in attn_terms:
+        t.K = len(matches[v][0])
     _stamp("fill")
-    pk2.send()
+    tt.send()
     _stamp("send")
-    plan = dict(terms_host=terms, terms_dev=base2 + t_off, nterms=nterms, coef_dev=base2 + coef_off, nout=nout,
-                ws=ws, grads=(gflat, goff, [(t.shape, _contig_strides(t.shape)) for t in inputs]),
-                keep=(early, pk2, pke, scr, sims, flog, text_seen))
-    out, loss = _LossFn.apply(plan, *inputs)
+    out, loss = tt.launch(keep=(early, pke, sims, flog, text_seen))
 
     _stamp("send_lossfn")
     # the reference's side channels: last video's per-block losses, fact / contrastive terms
@@ -794,7 +641,7 @@ def run(net, vb, compute_loss, early=None):
             saves[v]["pred"] = ph[fo[v]:fo[v + 1]].astype(np.int64)
             saves[v]["loss"] = d
     pending = PendingReadback(ready, lambda: fxf.status_raise(int(st_h[0]), dev), fill, nvid)
-    plan["readback"] = pending
+    tt.plan["readback"] = pending
     if not LAZY_READBACK:
         pending.resolve()
     return loss, pending.saves

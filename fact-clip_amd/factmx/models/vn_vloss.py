@@ -11,7 +11,7 @@ one-hot tables (blocks_SepVerbNoun.py:298-321, 487-496 over loss.py:195-277).  H
                      token term (FX_TERM_VNCLASS with null column, targets from the match: 0.5/Q); per
                      update block the f2a (axis 0) and a2f (axis 1) terms (FX_TERM_ATTN with interval
                      targets, 1/S); the coefficient matrix gives [video loss, per-block values]
-  fx_loss_terms_bwd  every logit tensor's gradient in one autograd node (vloss._LossFn).
+  fx_loss_terms_bwd  every logit tensor's gradient in one autograd node (termtable._LossFn).
 
 A video whose match pairs more than FX_LOSS_MAXK columns, or a model with ``cfg.FACT.trans``, takes
 the per-term path of Block.compute_loss.
@@ -21,16 +21,19 @@ functional.vn_match_cost_batch for every video and reads the costs back through 
 forward goes on (``BatchMatch``); after the host matching ONE table holds the terms above of every block of
 every video (``batch_plan``: [batch loss, per-video loss, per-video per-block values]), then
 functional.vn_eval_pred_batch and one read-back of predictions, loss values and the status word.
+
+``run`` and ``run_batch`` share ``_launch`` / ``_fill`` on models/termtable.TermTable and differ only in where a
+term's rows live: ``_sources`` (the blocks' own tensors, a batch of one) or ``_batch_sources`` (the stacked ``_bt``).
 """
-import ctypes
+import collections
 
 import numpy as np
 import torch
 
 from .. import functional as fxf
 from .. import native as nx
-from .vloss import (EarlyMatch, TableTooLarge, _LossFn, _Pack, _contig_strides, _pinned, class_weights, gt_segments,
-                    segment_weights)
+from .termtable import TermTable, _Pack
+from .vloss import EarlyMatch, TableTooLarge, _pinned, class_weights, gt_segments, segment_weights
 
 # The loss terms of a video of CUDA inputs from one term table (with blocks_SepVerbNoun.FUSED_LOSS);
 # False: one launch pair per class term and the eager cross-attention terms.
@@ -97,17 +100,131 @@ def _host_labels(crit, label):
     return np.asarray(lab)
 
 
+# ---------------------------------------------------------------------------
+# The table of one video or of a batch: where each term's rows live, and the one loop that fills it
+# ---------------------------------------------------------------------------
+
+# One term's rows: ``t`` the differentiated input, ``x`` the tensor the kernel reads (``t`` or a view of it),
+# ``xoff`` / ``goff`` the element offset of the video's first row in ``x`` and in ``t``'s gradient, R x C rows
+# with the element strides ``sr`` / ``sc`` of ``x`` and ``dsr`` / ``dsc`` of the (contiguous) gradient.
+_Src = collections.namedtuple("_Src", "t x xoff goff R C sr sc dsr dsc")
+# One block of one video: class terms, attention terms (None: an input block), its TDU intervals' addresses.
+_Blk = collections.namedtuple("_Blk", "frame seg token f2a a2f rs re")
+# One video: frames, matched columns, the addresses of its int32 labels, token targets and (ka, kgs, kge, ksw).
+_Vid = collections.namedtuple("_Vid", "T K lab tgt kcols")
+_KCOLS = (("ka", np.int32), ("kgs", np.int32), ("kge", np.int32), ("ksw", np.float32))
+
+
+def _class_src(t, x, row0, R, C, ldx):
+    """Rows ``row0 .. row0 + R`` of the (rows, C) class logits ``x`` of row stride ``ldx``."""
+    return _Src(t, x, row0 * ldx, row0 * C, R, C, ldx, 1, C, 1)
+
+
+def _attn_src(name, L, off, shape, st, S, Q):
+    """A video's attention logits read as (S, Q): its (Q, S) [f2a: log_softmax over the rows of each matched
+    column, axis 0] or (S, Q) [a2f: over the matched columns of each row, axis 1] block of ``shape`` and
+    element strides ``st`` at element ``off`` of the input ``L``; its gradient block is contiguous."""
+    if tuple(shape) != ((Q, S) if name == "f2a" else (S, Q)):
+        raise RuntimeError(f"vn_vloss: {name} logits {tuple(shape)} of {tuple(L.shape)} for {S} segments x {Q} tokens")
+    if name == "f2a":
+        return _Src(L, L, off, off, S, Q, st[1], st[0], 1, S)
+    return _Src(L, L, off, off, S, Q, st[0], st[1], Q, 1)
+
+
+def _sources(blocks, kinds, S, Q):
+    """``src[0][block]`` of one video from the blocks' own tensors: (R, 1, C) class logits, (1, Q, S) /
+    (1, S, Q) attention logits and the TDU's intervals -- a batch of one video."""
+    out = []
+    for blk, letter, Sk in zip(blocks, kinds, S):
+        cl = [_class_src(x3, x, 0, int(x.shape[0]), int(x.shape[1]), nx.ld(x))
+              for x3, x in ((x3, fxf._2d(x3)) for x3 in blk._clogits)]
+        at = [None, None]
+        if letter == "U":
+            at = [_attn_src(n_, L3, 0, L3.shape[1:], L3.stride()[1:], Sk, Q)
+                  for n_, L3 in (("f2a", blk.f2a_attn_logit), ("a2f", blk.a2f_attn_logit))]
+        out.append(_Blk(*cl, *at, blk.tdu.start32.data_ptr(), blk.tdu.end32.data_ptr()))
+    return [out]
+
+
+def _batch_sources(bts, kinds, Ts, fo, Q):
+    """``src[video][block]`` from the blocks' stacked ``_bt`` tensors: video v's frame rows at ``fo[v]``,
+    segment rows at ``s_off[v]``, token rows at ``v * Q``, and its (Q, S_v) / (S_v, Q) attention block at
+    element ``Q * s_off[v]`` of the logits (every video's block back to back, the element step the tensor's)."""
+    out = [[] for _ in Ts]
+    for bt, letter in zip(bts, kinds):
+        S, s_off = bt["S"], bt["s_off"]
+        if letter == "U":
+            Lf, La = bt["f2a_lg"], bt["a2f_lg"]
+            for n_, L in (("f2a", Lf), ("a2f", La)):
+                if L.numel() != Q * s_off[-1]:
+                    raise RuntimeError(f"vn_vloss: {n_} logits {tuple(L.shape)} for {s_off[-1]} segments x {Q} tokens")
+            ef, ea = Lf.view(-1).stride(0), La.view(-1).stride(0)
+        (f, fC, fld), (s, sC, sld), (a, aC, ald) = ((x, int(x.shape[1]), nx.ld(x))
+                                                    for x in (bt["f_cl"], bt["seg_cl"], bt["a_cl"]))
+        for v, T in enumerate(Ts):
+            Sv, s0 = S[v], s_off[v]
+            at = [None, None]
+            if letter == "U":
+                at = [_attn_src("f2a", Lf, Q * s0 * ef, (Q, Sv), (Sv * ef, ef), Sv, Q),
+                      _attn_src("a2f", La, Q * s0 * ea, (Sv, Q), (Q * ea, ea), Sv, Q)]
+            out[v].append(_Blk(_class_src(f, f, fo[v], T, fC, fld), _class_src(s, s, s0, Sv, sC, sld),
+                               _class_src(a, a, v * Q, Q, aC, ald), *at,
+                               bt["local"][v][1].data_ptr(), bt["local"][v][2].data_ptr()))
+    return out
+
+
+def _inputs(src):
+    """Every differentiated input of the sources, block by block (TermTable drops the repeats)."""
+    return [s.t for blks in src for b in blks for s in b[:5] if s is not None]
+
+
+def _fill(tt, rows, src, vids, w, vn):
+    """Every term of ``rows`` ((video, block, name, c_ce, c_sm)) in order -- the kernels' summation order --
+    from ``src[video][block]`` and the per-video ``vids``, then the scratch layout.  ``w``: the class weights'
+    address, ``vn``: TermTable.vn_pair's two mappings."""
+    for v, k, name, c_ce, c_sm in rows:
+        b, pv = src[v][k], vids[v]
+        s = getattr(b, name)
+        x = s.x.data_ptr() + 4 * s.xoff
+        if name in ("f2a", "a2f"):
+            t = tt.add(nx.TERM_ATTN, s.R, s.C, x, s.sr, s.sc, s.t, s.goff, s.dsr, s.dsc, c_ce, c_sm, pv.K)
+            t.axis, t.K, t.rs, t.re = (0 if name == "f2a" else 1), pv.K, b.rs, b.re
+            t.ka, t.kgs, t.kge, t.ksw = pv.kcols
+        else:
+            t = tt.add(nx.TERM_VNCLASS, s.R, s.C, x, s.sr, s.sc, s.t, s.goff, s.dsr, s.dsc, c_ce, c_sm)
+            t.w = w
+            t.vn, t.vn_host = vn[1 if name == "token" else 0]
+            if name == "token":
+                t.y = pv.tgt
+            else:
+                t.y = pv.lab
+                if name == "seg":
+                    t.rs, t.re, t.D = b.rs, b.re, pv.T
+    tt.lay_out()
+
+
+def _launch(pk, dev, rows, coef, src, mts, Ts, lab, w, vnmap, keep):
+    """The table of ``rows`` on the pack ``pk`` (the caller's own arrays reserved), sent and run: (out, loss).
+    ``mts[v]``: video v's match tables; ``lab[v]`` / ``w``: (pack, offset) of its int32 labels / of the class
+    weights -- ``pk`` itself or a pack sent earlier."""
+    o_tgt = [pk.array(mt["tgt"], np.int32) for mt in mts]
+    o_k = [[pk.array(mt[n_], dt) for n_, dt in _KCOLS] for mt in mts]
+    tt = TermTable(pk, dev, _inputs(src), coef, nvn=2)
+    base = tt.base
+    vids = [_Vid(Ts[v], mt["K"], lab[v][0].base + lab[v][1], base + o_tgt[v], [base + o for o in o_k[v]])
+            for v, mt in enumerate(mts)]
+    _fill(tt, rows, src, vids, w[0].base + w[1], tt.vn_pair(vnmap))
+    tt.send()
+    return tt.launch(keep=(src, keep))
+
+
 def run(net, crit, match, label):
     """The video loss of the blocks' saved class logits and attention logits for ``match``; sets
     ``net.loss_list`` (views of the table's per-block outputs).  None: the match is too large for the
     table, nothing was launched."""
-    lib = nx.load()
-    cfg = net.cfg
     blocks = list(net.block_list)
-    vnmap = net.vnmap
-    A, V, N = vnmap.num_actions, vnmap.num_verbs, vnmap.num_nouns
+    A = net.vnmap.num_actions
     f0 = blocks[0]._clogits[0]
-    dev = f0.device
     T, Q = int(f0.shape[0]), int(blocks[0]._clogits[2].shape[0])
     lab = _host_labels(crit, label)
     gts = gt_segments(lab)
@@ -115,96 +232,13 @@ def run(net, crit, match, label):
     mt = match_tables(crit, gts, match, Q, A, cw)
     if mt is None:
         return None
-    K = mt["K"]
     kinds = ["U" if hasattr(blk, "a2f_layer") else "I" for blk in blocks]
     S = [int(blk.tdu.num_seg) for blk in blocks]
-    rows, coef = term_plan(kinds, T, S, Q, A, float(cfg.Loss.sw))
-    nterms, nout = len(rows), 1 + len(blocks)
-
-    # every differentiated input, its gradient a view of ONE flat allocation
-    inputs = []
-    for blk, letter in zip(blocks, kinds):
-        inputs.extend(blk._clogits)
-        if letter == "U":
-            inputs.extend((blk.f2a_attn_logit, blk.a2f_attn_logit))
-    sizes = [(t.numel() + 63) & ~63 for t in inputs]
-    goff = [0]
-    for n_ in sizes[:-1]:
-        goff.append(goff[-1] + n_)
-    gflat = torch.empty(sum(sizes), device=dev, dtype=torch.float32)
-    gaddr = {id(t): gflat.data_ptr() + 4 * o for t, o in zip(inputs, goff)}
-
-    pk = _Pack()
-    o_lab = pk.array(lab, np.int32)
-    o_cw = pk.array(cw, np.float32)
-    o_tgt = pk.array(mt["tgt"], np.int32)
-    o_k = [pk.array(mt[n_], dt) for n_, dt in (("ka", np.int32), ("kgs", np.int32), ("kge", np.int32),
-                                               ("ksw", np.float32))]
-    o_coef = pk.array(coef, np.float32)
-    o_vn, vnt = pk.structs(nx.VnTerm, 2)
-    o_t, terms = pk.structs(nx.LossTerm, nterms)
-    base = pk.alloc(dev)
-    vids, nids = vnmap.tables(dev)
-    for j, (n1, n2, null) in enumerate(((V, N, 0), (V + 1, N + 1, 1))):
-        m = vnt[j]
-        m.n1, m.n2, m.A, m.null = n1, n2, A, null
-        m.vids, m.nids = vids.data_ptr(), nids.data_ptr()
-        m.voff, m.vlist, m.noff, m.nlist = (t.data_ptr() for t in vnmap.csr(dev, n1, n2))
-    vn_dev = [base + o_vn + j * ctypes.sizeof(nx.VnTerm) for j in range(2)]
-    vn_host = [ctypes.addressof(vnt[j]) for j in range(2)]
-
-    slots = []
-    for i, (k, name, c_ce, c_sm) in enumerate(rows):
-        blk = blocks[k]
-        t = terms[i]
-        t.slot, t.c_ce, t.c_sm = i, c_ce, c_sm
-        if name in ("frame", "seg", "token"):
-            x3 = blk._clogits[("frame", "seg", "token").index(name)]
-            x = fxf._2d(x3)
-            j = 1 if name == "token" else 0
-            t.kind, t.R, t.C = nx.TERM_VNCLASS, int(x.shape[0]), int(x.shape[1])
-            t.x, t.sr, t.sc = x.data_ptr(), nx.ld(x), 1
-            t.dx, t.dsr, t.dsc = gaddr[id(x3)], t.C, 1
-            t.w, t.vn, t.vn_host = base + o_cw, vn_dev[j], vn_host[j]
-            if name == "token":
-                t.y = base + o_tgt
-            else:
-                t.y = base + o_lab
-                if name == "seg":
-                    t.rs, t.re, t.D = blk.tdu.start32.data_ptr(), blk.tdu.end32.data_ptr(), T
-            slots.append((2 * t.R, 0, 0))
-        else:
-            # f2a logits (1, Q, S) read as (S, Q): log_softmax over the rows of each matched column (axis 0);
-            # a2f logits (1, S, Q): log_softmax over the matched columns of each row (axis 1)
-            L3 = blk.f2a_attn_logit if name == "f2a" else blk.a2f_attn_logit
-            L = L3[0].t() if name == "f2a" else L3[0]
-            R, C = int(L.shape[0]), int(L.shape[1])
-            if (R, C) != (S[k], Q):
-                raise RuntimeError(f"vn_vloss: {name} logits {tuple(L3.shape)} for {S[k]} segments x {Q} tokens")
-            d3 = _contig_strides(L3.shape)
-            t.kind, t.R, t.C, t.axis, t.K = nx.TERM_ATTN, R, C, (0 if name == "f2a" else 1), K
-            t.x, t.sr, t.sc = L.data_ptr(), L.stride(0), L.stride(1)
-            t.dx = gaddr[id(L3)]
-            t.dsr, t.dsc = (d3[2], d3[1]) if name == "f2a" else (d3[1], d3[2])
-            t.rs, t.re = blk.tdu.start32.data_ptr(), blk.tdu.end32.data_ptr()
-            t.ka, t.kgs, t.kge, t.ksw = (base + o for o in o_k)
-            slots.append((R, R + K, K))
-    sc_, offs = 0, []
-    for sz in slots:
-        o3 = []
-        for n_ in sz:
-            o3.append(sc_)
-            sc_ += (max(n_, 1) + 3) & ~3
-        offs.append(o3)
-    scr = torch.empty(sc_, device=dev, dtype=torch.float32)
-    for t, o3 in zip(terms, offs):
-        t.lse, t.lse2, t.colz = (scr.data_ptr() + 4 * o for o in o3)
-    ws = torch.empty(max(lib.fx_loss_terms_workspace_floats(nterms), 1), device=dev, dtype=torch.float32)
-    pk.send()
-    plan = dict(terms_host=terms, terms_dev=base + o_t, nterms=nterms, coef_dev=base + o_coef, nout=nout, ws=ws,
-                grads=(gflat, goff, [(t.shape, _contig_strides(t.shape)) for t in inputs]),
-                keep=(pk, scr, vids, nids, [blk.tdu for blk in blocks], inputs))   # (the backward reads the logits)
-    out, loss = _LossFn.apply(plan, *inputs)
+    rows, coef = term_plan(kinds, T, S, Q, A, float(net.cfg.Loss.sw))
+    pk = _Pack()                               # (the labels and the class weights travel with the table)
+    o_lab, o_cw = pk.array(lab, np.int32), pk.array(cw, np.float32)
+    out, loss = _launch(pk, f0.device, [(0,) + r for r in rows], coef, _sources(blocks, kinds, S, Q), [mt], [T],
+                        [(pk, o_lab)], (pk, o_cw), net.vnmap, [blk.tdu for blk in blocks])
     net.loss_list = [out[1 + k] for k in range(len(blocks))]
     return loss
 
@@ -317,11 +351,10 @@ def run_batch(net, vb, compute_loss, early=None):
     the loss values and the status word.  Returns FACT.forward's value: save_list, or (loss, save_list).
     Raises vloss.TableTooLarge, with nothing but the costs launched, when a video's match pairs more than
     FX_LOSS_MAXK columns."""
-    lib = nx.load()
     cfg = net.cfg
     blocks = list(net.block_list)
     vnmap = net.vnmap
-    A, V, N = vnmap.num_actions, vnmap.num_verbs, vnmap.num_nouns
+    A = vnmap.num_actions
     nvid, Q, Ts, fo = vb.nvid, vb.Q, vb.Ts, vb.f_off
     nb = len(blocks)
     dev = blocks[-1]._bt["f_cl"].device
@@ -336,95 +369,11 @@ def run_batch(net, vb, compute_loss, early=None):
         if big:
             raise TableTooLarge(big)
         kinds = ["U" if hasattr(blk, "a2f_layer") else "I" for blk in blocks]
-        rows, coef = batch_plan(kinds, Ts, [blk._bt["S"] for blk in blocks], Q, A, float(cfg.Loss.sw))
-        nterms, nout = len(rows), coef.shape[0]
-
-        # every differentiated input (the blocks' stacked logits), its gradient a view of ONE flat allocation
-        inputs = []
-        for blk, letter in zip(blocks, kinds):
-            bt = blk._bt
-            inputs.extend((bt["f_cl"], bt["seg_cl"], bt["a_cl"]))
-            if letter == "U":
-                inputs.extend((bt["f2a_lg"], bt["a2f_lg"]))
-        sizes = [(t.numel() + 63) & ~63 for t in inputs]
-        goff = [0]
-        for n_ in sizes[:-1]:
-            goff.append(goff[-1] + n_)
-        gflat = torch.empty(sum(sizes), device=dev, dtype=torch.float32)
-        gaddr = {id(t): gflat.data_ptr() + 4 * o for t, o in zip(inputs, goff)}
-
-        pk = _Pack()
-        o_tgt = [pk.array(mt["tgt"], np.int32) for mt in mts]
-        o_k = [[pk.array(mt[n_], dt) for n_, dt in (("ka", np.int32), ("kgs", np.int32), ("kge", np.int32),
-                                                     ("ksw", np.float32))] for mt in mts]
-        o_coef = pk.array(coef, np.float32)
-        o_vn, vnt = pk.structs(nx.VnTerm, 2)
-        o_t, terms = pk.structs(nx.LossTerm, nterms)
-        base = pk.alloc(dev)
-        vids, nids = vnmap.tables(dev)
-        for j, (n1, n2, null) in enumerate(((V, N, 0), (V + 1, N + 1, 1))):
-            m = vnt[j]
-            m.n1, m.n2, m.A, m.null = n1, n2, A, null
-            m.vids, m.nids = vids.data_ptr(), nids.data_ptr()
-            m.voff, m.vlist, m.noff, m.nlist = (t.data_ptr() for t in vnmap.csr(dev, n1, n2))
-        vn_dev = [base + o_vn + j * ctypes.sizeof(nx.VnTerm) for j in range(2)]
-        vn_host = [ctypes.addressof(vnt[j]) for j in range(2)]
-        cw_p = early.base + early.cw_off
-
-        slots = []
-        for i, (v, k, name, c_ce, c_sm) in enumerate(rows):
-            bt = blocks[k]._bt
-            t = terms[i]
-            t.slot, t.c_ce, t.c_sm = i, c_ce, c_sm
-            Sv, s0 = bt["S"][v], bt["s_off"][v]
-            rs, re = bt["local"][v][1].data_ptr(), bt["local"][v][2].data_ptr()
-            if name in ("frame", "seg", "token"):
-                x = bt[{"frame": "f_cl", "seg": "seg_cl", "token": "a_cl"}[name]]
-                row0, R = {"frame": (fo[v], Ts[v]), "seg": (s0, Sv), "token": (v * Q, Q)}[name]
-                C, ldx = int(x.shape[1]), nx.ld(x)
-                j = 1 if name == "token" else 0
-                t.kind, t.R, t.C = nx.TERM_VNCLASS, R, C
-                t.x, t.sr, t.sc = x.data_ptr() + 4 * row0 * ldx, ldx, 1
-                t.dx, t.dsr, t.dsc = gaddr[id(x)] + 4 * row0 * C, C, 1
-                t.w, t.vn, t.vn_host = cw_p, vn_dev[j], vn_host[j]
-                if name == "token":
-                    t.y = base + o_tgt[v]
-                else:
-                    t.y = early.base + early.lab_off[v]
-                    if name == "seg":
-                        t.rs, t.re, t.D = rs, re, Ts[v]
-                slots.append((2 * R, 0, 0))
-            else:
-                # video v's f2a logits (Q, S_v) read as (S_v, Q): log_softmax over the rows of each matched
-                # column (axis 0); its a2f logits (S_v, Q): log_softmax over the matched columns of each row
-                L = bt["f2a_lg" if name == "f2a" else "a2f_lg"]
-                if L.numel() != Q * bt["s_off"][-1]:
-                    raise RuntimeError(f"vn_vloss: {name} logits {tuple(L.shape)} for {bt['s_off'][-1]} segments "
-                                       f"x {Q} tokens")
-                K = mts[v]["K"]
-                sr, sc = (1, Sv) if name == "f2a" else (Q, 1)
-                t.kind, t.R, t.C, t.axis, t.K = nx.TERM_ATTN, Sv, Q, (0 if name == "f2a" else 1), K
-                t.x, t.sr, t.sc = L.data_ptr() + 4 * Q * s0, sr, sc
-                t.dx, t.dsr, t.dsc = gaddr[id(L)] + 4 * Q * s0, sr, sc
-                t.rs, t.re = rs, re
-                t.ka, t.kgs, t.kge, t.ksw = (base + o for o in o_k[v])
-                slots.append((Sv, Sv + K, K))
-        sc_, offs = 0, []
-        for sz in slots:
-            o3 = []
-            for n_ in sz:
-                o3.append(sc_)
-                sc_ += (max(n_, 1) + 3) & ~3
-            offs.append(o3)
-        scr = torch.empty(sc_, device=dev, dtype=torch.float32)
-        for t, o3 in zip(terms, offs):
-            t.lse, t.lse2, t.colz = (scr.data_ptr() + 4 * o for o in o3)
-        ws = torch.empty(max(lib.fx_loss_terms_workspace_floats(nterms), 1), device=dev, dtype=torch.float32)
-        pk.send()
-        plan = dict(terms_host=terms, terms_dev=base + o_t, nterms=nterms, coef_dev=base + o_coef, nout=nout, ws=ws,
-                    grads=(gflat, goff, [(t.shape, _contig_strides(t.shape)) for t in inputs]),
-                    keep=(early, pk, scr, vids, nids, [blk._bt for blk in blocks], inputs))
-        out, loss = _LossFn.apply(plan, *inputs)
+        bts = [blk._bt for blk in blocks]
+        rows, coef = batch_plan(kinds, Ts, [bt["S"] for bt in bts], Q, A, float(cfg.Loss.sw))
+        lab, w = [(early.pk, o) for o in early.lab_off], (early.pk, early.cw_off)
+        out, loss = _launch(_Pack(), dev, rows, coef, _batch_sources(bts, kinds, Ts, fo, Q), mts, Ts, lab, w, vnmap,
+                            (early, bts))
         o = 1 + nvid + (nvid - 1) * nb
         net.loss_list = [out[o + k] for k in range(nb)]        # the last video's per-block values
 

@@ -8,8 +8,6 @@ gradients 2e-5 x (1 + max|ref|).
 Model level: ``tiny_vn`` with the table on and off, and the ``tiny_vn_o2m`` fixture (o2m matching with
 more than 64 matched columns) against the reference's values.
 """
-import ctypes
-
 import numpy as np
 import pytest
 import torch
@@ -17,7 +15,7 @@ import torch
 import paramgen as pg
 from factmx import functional as fxf
 from factmx import native as nx
-from factmx.models.vloss import _Pack, _LossFn, _contig_strides
+from factmx.models.termtable import TermTable, _Pack
 from helpers import load_fixture, tiny_meta, cfg_from_meta, tiny_inputs, check_grad
 from test_gpu_verbnoun import _mapping, _close
 from test_gpu_vn_loss import loss_case, seg_case, _r
@@ -35,58 +33,36 @@ def run_table(specs):
     """One term table of ``specs`` (dicts: VNCLASS terms ``x, m, null, y, w, c_ce, c_sm[, rs, re, D]``, ATTN
     terms ``L, axis, ka, kgs, kge, ksw, rs, re, c_ce``): out = [UP * sum of the terms, each term], the
     backward of out[0].  Returns (out, [gradient of each term's logits])."""
-    lib = nx.load()
     n = len(specs)
     inputs = [(s["x"] if "x" in s else s["L"]) for s in specs]
-    sizes = [(t.numel() + 63) & ~63 for t in inputs]
-    goff = [int(v) for v in np.cumsum([0] + sizes[:-1])]
-    gflat = torch.full((sum(sizes),), float("nan"), device=DEV)
     coef = np.zeros((1 + n, n), dtype=np.float32)
     coef[0, :] = UP
     coef[1:, :] = np.eye(n)
-    pk = _Pack()
-    o_coef = pk.array(coef, np.float32)
-    o_vn, vnt = pk.structs(nx.VnTerm, n)
-    o_t, terms = pk.structs(nx.LossTerm, n)
-    base = pk.alloc(DEV)
-    keep = []
-    scr = []
+    tt = TermTable(_Pack(), DEV, inputs, coef, nvn=n)       # (every VNCLASS term its own mapping)
+    tt.gflat.fill_(float("nan"))
     for i, s in enumerate(specs):
-        t = terms[i]
-        t.slot, t.c_ce, t.c_sm = i, s["c_ce"], s.get("c_sm", 0.0)
-        t.dx = gflat.data_ptr() + 4 * goff[i]
+        c_ce, c_sm = s["c_ce"], s.get("c_sm", 0.0)
         if "x" in s:
             x, m, null = s["x"], s["m"], s["null"]
-            n1, n2 = m.num_verbs + null, m.num_nouns + null
-            v = vnt[i]
-            v.n1, v.n2, v.A, v.null = n1, n2, m.num_actions, null
-            v.vids, v.nids = (a.data_ptr() for a in m.tables(x.device))
-            v.voff, v.vlist, v.noff, v.nlist = (a.data_ptr() for a in m.csr(x.device, n1, n2))
-            t.kind, t.R, t.C = nx.TERM_VNCLASS, x.shape[0], n1 + n2
-            t.x, t.sr, t.sc, t.dsr, t.dsc = x.data_ptr(), x.stride(0), 1, x.shape[1], 1
-            t.vn, t.vn_host = base + o_vn + i * ctypes.sizeof(nx.VnTerm), ctypes.addressof(v)
+            C = m.num_verbs + m.num_nouns + 2 * null
+            t = tt.add(nx.TERM_VNCLASS, x.shape[0], C, x.data_ptr(), x.stride(0), 1, x, 0, x.shape[1], 1, c_ce, c_sm)
+            t.vn, t.vn_host = tt.vn(i, m, null)
             t.w = s["w"].data_ptr()
             if s.get("y") is not None:
                 t.y = s["y"].data_ptr()
             if "rs" in s:
                 t.rs, t.re, t.D = s["rs"].data_ptr(), s["re"].data_ptr(), s["D"]
-            sz = (2 * t.R, 1, 1)
         else:
             L = s["L"]
             K = len(s["ka"])
-            t.kind, t.R, t.C, t.axis, t.K = nx.TERM_ATTN, L.shape[0], L.shape[1], s["axis"], K
-            t.x, t.sr, t.sc, t.dsr, t.dsc = L.data_ptr(), L.stride(0), L.stride(1), L.shape[1], 1
+            t = tt.add(nx.TERM_ATTN, L.shape[0], L.shape[1], L.data_ptr(), L.stride(0), L.stride(1), L, 0,
+                       L.shape[1], 1, c_ce, c_sm, K)
+            t.axis, t.K = s["axis"], K
             t.rs, t.re = s["rs"].data_ptr(), s["re"].data_ptr()
             t.ka, t.kgs, t.kge, t.ksw = (s[k].data_ptr() for k in ("ka", "kgs", "kge", "ksw"))
-            sz = (t.R, t.R + K, K)
-        bufs = [torch.empty(max(z, 1), device=DEV) for z in sz]
-        t.lse, t.lse2, t.colz = (b.data_ptr() for b in bufs)
-        scr.append(bufs)
-    pk.send()
-    ws = torch.empty(lib.fx_loss_terms_workspace_floats(n), device=DEV)
-    plan = dict(terms_host=terms, terms_dev=base + o_t, nterms=n, coef_dev=base + o_coef, nout=1 + n, ws=ws,
-                grads=(gflat, goff, [(t.shape, _contig_strides(t.shape)) for t in inputs]), keep=(pk, scr, keep, specs))
-    out, loss = _LossFn.apply(plan, *inputs)
+    tt.lay_out()
+    tt.send()
+    out, loss = tt.launch(keep=specs)
     grads = torch.autograd.grad(loss, inputs)
     torch.cuda.synchronize()
     return out.detach(), [g.clone() for g in grads]
