@@ -6,6 +6,14 @@ Same constructors, attribute names read by losses / eval / scripts
 ``projected_frame_embeddings``, ``fact_loss``, ``contrastive_loss``),
 state_dict keys and ``forward(seq_list, label_list, compute_loss)``
 contract.  Compute runs on the HIP kernels through factmx.functional.
+
+What the verb/noun model (models/blocks_SepVerbNoun.py) shares lives here once: ``Block``'s branch
+constructors, ``_TDU`` (the segment-level flow of one video and of stacked videos; a block family gives it a
+``ClassHeads``-like description of its class columns and its own side-channel storage), ``_save_views`` (the
+per-video split views ``_vrec`` and the stacked ``_bt`` of every ``forward_batch``) and ``_FACTBase``'s
+``_run_blocks`` / ``_forward_batch``.  Two switches of the model differ between the families on purpose:
+``dp_marks`` (block inputs marked for factmx.dp: this file's models only) and ``match_before_merge`` (where
+the last block starts the loss phase's matching, see ``_TDU.forward_batch``).
 """
 import torch
 import torch.nn as nn
@@ -87,6 +95,28 @@ def _lazy_attr(name):
     return property(get, put)
 
 
+class ClassHeads:
+    """The class columns a block family appends to its features: how frame / segment rows and token rows
+    (one more column: the null class) split into (feature, class logits), and how frames are segmented
+    by their class probabilities, for one video and for stacked videos.  Nothing else about the heads
+    is known to the shared flow (_TDU); blocks_SepVerbNoun.VerbNounHeads is the other family."""
+
+    def __init__(self, nclass):
+        self.nclass = nclass
+
+    def split(self, x):
+        return fxf.process_feature(x, self.nclass)
+
+    def split_tokens(self, x):
+        return fxf.process_feature(x, self.nclass + 1)
+
+    def segment(self, f2):
+        return basic.TemporalDownsampleUpsample.from_probs(f2, f2.shape[1] - self.nclass, self.nclass)
+
+    def segment_batch(self, f2, f_off, hook):
+        return fxf.segments_from_probs_batched(f2, f2.shape[1] - self.nclass, self.nclass, f_off, hook)
+
+
 class Block(nn.Module):
     """blocks.py:180-281."""
 
@@ -99,6 +129,11 @@ class Block(nn.Module):
 
     def process_feature(self, feature, nclass):
         out, clogit = fxf.process_feature(feature, nclass)
+        return out.unsqueeze(1), clogit.unsqueeze(1)
+
+    def _split(self, feature, tokens=False):
+        """``process_feature`` with the class columns of the block's family (``self.heads``)."""
+        out, clogit = self.heads.split_tokens(feature) if tokens else self.heads.split(feature)
         return out.unsqueeze(1), clogit.unsqueeze(1)
 
     def create_fbranch(self, cfg, in_dim=None, f_inmap=False):
@@ -175,6 +210,46 @@ def _frame_branch_batch(branch, f, vb):
     return fxf.mstcn(branch, f, T=vb.T or 0, nvid=vb.nvid, seq_off=so)
 
 
+def _save_views(blk, vb, f_cl, a_cl, a_feat=None, seg=None, attn=None):
+    """The side channels of a block's stacked outputs: ``blk._vrec``, per video the views through ONE split
+    node per tensor (_VideoBatch.frames), and ``blk._bt``, the stacked tensors the loss phase reads.
+    ``a_feat``: (token output, its class columns); ``seg``: (segment record of _TDU._downsample_batch,
+    segment class logits); ``attn``: (f2a logits, f2a attention, a2f logits, a2f attention) over the
+    segments if ``seg`` is given, else over the frames.  Video v's record holds frame_clogit (T, 1, C),
+    action_clogit (Q, 1, C + 1), action_feature (Q, 1, A), seg_clogit (S, 1, C) and tdu, f2a_attn(_logit)
+    (1, Q, n) and a2f_attn(_logit) (1, n, Q) with n = S or T, each as far as given.  Returns the records:
+    a family rewrites them where its attributes differ."""
+    Q, n = vb.Q, vb.Ts
+    bt = dict(f_cl=f_cl, a_cl=a_cl)
+    fc, ac = vb.frames(f_cl), vb.tokens(a_cl)
+    if a_feat is not None:
+        ao, ncol = vb.tokens(a_feat[0]), a_feat[1]
+    if seg is not None:
+        sg, seg_cl = seg
+        n = sg["S"]
+        sc = torch.split(seg_cl, n)
+        bt.update(seg_cl=seg_cl, S=n, s_off=sg["s_off"], local=sg["local"])
+    if attn is not None:
+        f2a_lg, f2a_at, a2f_lg, a2f_at = attn
+        qn = [Q * k for k in n]
+        fat, aat, flg, alg = (torch.split(t, qn) for t in (f2a_at, a2f_at, f2a_lg, a2f_lg))
+        bt.update(f2a_lg=f2a_lg, a2f_lg=a2f_lg, a2f_at=a2f_at)
+    recs = []
+    for v in range(vb.nvid):
+        rec = dict(frame_clogit=fc[v].unsqueeze(1), action_clogit=ac[v].unsqueeze(1))
+        if a_feat is not None:
+            rec["action_feature"] = ao[v][:, :-ncol].unsqueeze(1)
+        if seg is not None:
+            rec.update(seg_clogit=sc[v].unsqueeze(1), tdu=basic.TemporalDownsampleUpsample(*sg["local"][v]))
+        if attn is not None:
+            k = n[v]
+            rec.update(f2a_attn=fat[v].view(1, Q, k), a2f_attn=aat[v].view(1, k, Q),
+                       f2a_attn_logit=flg[v].view(1, Q, k), a2f_attn_logit=alg[v].view(1, k, Q))
+        recs.append(rec)
+    blk.__dict__["_vrec"], blk.__dict__["_bt"] = recs, bt     # (no nn.Module.__setattr__ walk)
+    return recs
+
+
 class InputBlock(Block):
     """blocks.py:284-320."""
 
@@ -215,11 +290,7 @@ class InputBlock(Block):
         a = fxf.decoder(self.action_branch, a2, f_out, pos=fpos, query_pos=apos, nvid=vb.nvid,
                         mem_off=vb.f_off if vb.ragged else None)
         a_out, a_cl = fxf.process_feature(a, self.nclass + 1)
-        n = self.nclass + 1
-        fc, ac, ao = vb.frames(f_cl), vb.tokens(a_cl), vb.tokens(a_out)
-        self._vrec = [dict(frame_clogit=fc[v].unsqueeze(1), action_clogit=ac[v].unsqueeze(1),
-                           action_feature=ao[v][:, :-n].unsqueeze(1)) for v in range(vb.nvid)]
-        self.__dict__["_bt"] = dict(f_cl=f_cl, a_cl=a_cl)
+        _save_views(self, vb, f_cl, a_cl, (a_out, self.nclass + 1))
         return f_out, a_out
 
     def compute_loss(self, criterion, match=None):
@@ -272,19 +343,7 @@ class UpdateBlock(Block):
             # device works through the frame branch just issued, its cost launch queues behind it
             vb.on_a2f(vb, a_cl, a2f_at)
         f_out, f_cl = fxf.process_feature(f, self.nclass)
-        n, Q = self.nclass + 1, vb.Q
-        recs = []
-        fc, ac, ao = vb.frames(f_cl), vb.tokens(a_cl), vb.tokens(a_out)
-        qt = [Q * T for T in vb.Ts]
-        fat, aat, flg, alg = (torch.split(t, qt) for t in (f2a_at, a2f_at, f2a_lg, a2f_lg))
-        for v in range(vb.nvid):
-            T = vb.Ts[v]
-            recs.append(dict(frame_clogit=fc[v].unsqueeze(1), action_clogit=ac[v].unsqueeze(1),
-                             action_feature=ao[v][:, :-n].unsqueeze(1),
-                             f2a_attn=fat[v].view(1, Q, T), a2f_attn=aat[v].view(1, T, Q),
-                             f2a_attn_logit=flg[v].view(1, Q, T), a2f_attn_logit=alg[v].view(1, T, Q)))
-        self.__dict__["_vrec"] = recs     # (plain attributes: no nn.Module.__setattr__ walk)
-        self.__dict__["_bt"] = dict(f_cl=f_cl, a_cl=a_cl, f2a_lg=f2a_lg, a2f_lg=a2f_lg, a2f_at=a2f_at)
+        _save_views(self, vb, f_cl, a_cl, (a_out, self.nclass + 1), attn=(f2a_lg, f2a_at, a2f_lg, a2f_at))
         return f_out, a_out
 
     def compute_loss(self, criterion, match=None):
@@ -298,29 +357,32 @@ class UpdateBlock(Block):
         return _sum_terms([atk, f2a, a2f, criterion.frame_terms(self.frame_clogit, 1.0, sw)])
 
 
-class UpdateBlockTDU(Block):
-    """blocks.py:385-497: segment-level update with device-side temporal down/up-sampling."""
+class _TDU:
+    """The segment-level (temporal down/up-sampling) flow of every block family, mixed into a Block: the
+    plain UpdateBlockTDU below and blocks_SepVerbNoun's UpdateBlockTDU / InputBlockTDU.  A family supplies
+    its class columns (``self.heads``) and how it stores the side channels: ``_save`` (one video) and
+    ``_save_batch`` (stacked videos)."""
 
-    def __init__(self, cfg, nclass):
-        super().__init__()
-        self.cfg = cfg
-        self.nclass = nclass
-        bcfg = cfg.BU
-        self.frame_branch = self.create_fbranch(bcfg)
-        self.seg_update = nn.GRU(bcfg.hid_dim, bcfg.hid_dim // 2, bcfg.s_layers, bidirectional=True)
+    def _create_seg(self, bcfg, s_layers):
+        self.seg_update = nn.GRU(bcfg.hid_dim, bcfg.hid_dim // 2, s_layers, bidirectional=True)
         self.seg_combine = nn.Linear(bcfg.hid_dim, bcfg.hid_dim)
+
+    def _create_update(self, bcfg):
+        """The update block's sub-modules, in the reference's creation order (seeded initialisation and
+        the parameter order depend on it)."""
+        self.frame_branch = self.create_fbranch(bcfg)
+        self._create_seg(bcfg, bcfg.s_layers)
         self.f2a_layer = self.create_cross_attention(bcfg, bcfg.a_dim)
         self.action_branch = self.create_abranch(bcfg)
         self.a2f_layer = self.create_cross_attention(bcfg, bcfg.f_dim)
         self.sf_merge = nn.Sequential(nn.Linear(bcfg.hid_dim + bcfg.f_dim, bcfg.f_dim), nn.ReLU())
 
     def temporal_downsample(self, frame_feature):
-        f2 = fxf._2d(frame_feature)
-        tdu = basic.TemporalDownsampleUpsample.from_probs(f2, f2.shape[1] - self.nclass, self.nclass)
+        tdu = self.heads.segment(fxf._2d(frame_feature))
         seg = tdu.feature_frame2seg(frame_feature)
         seg = fxf.gru(self.seg_update, seg, relu=True)      # relu(seg_update(seg)) (blocks.py:432)
         seg = fxf.linear(seg, self.seg_combine.weight, self.seg_combine.bias).unsqueeze(1)
-        seg, seg_clogit = self.process_feature(seg, self.nclass)
+        seg, seg_clogit = self._split(seg)
         return tdu, seg, seg_clogit
 
     def temporal_upsample(self, tdu, seg_feature, frame_feature):
@@ -334,11 +396,72 @@ class UpdateBlockTDU(Block):
         seg_pos = None if frame_pos is None else frame_pos[tdu.centers()]
         action_feature = self.f2a_layer(seg_feature, action_feature, X_pos=seg_pos, Y_pos=action_pos)
         action_feature = self.action_branch(action_feature, action_pos)
-        action_feature, action_clogit = self.process_feature(action_feature, self.nclass + 1)
+        action_feature, action_clogit = self._split(action_feature, tokens=True)
         seg_feature = self.a2f_layer(action_feature, seg_feature, X_pos=action_pos, Y_pos=seg_pos)
         frame_feature = self.temporal_upsample(tdu, seg_feature, frame_feature)
         frame_feature = self.frame_branch(frame_feature)
-        frame_feature, frame_clogit = self.process_feature(frame_feature, self.nclass)
+        frame_feature, frame_clogit = self._split(frame_feature)
+        self._save(tdu, frame_clogit, seg_clogit, action_clogit, action_feature)
+        return frame_feature, action_feature
+
+    def _downsample_batch(self, f2, fpos, vb):
+        """``temporal_downsample`` over the stacked videos: one segmentation launch + ONE host read of every
+        video's S (the first TDU block: the loss phase's label-only host work runs while the host waits),
+        segment means on the global tables, the BiGRU over the ragged segment rows.  Returns the segment
+        record and (seg feature, seg class logits, seg positions)."""
+        hook, vb.while_waiting = vb.while_waiting, None
+        S, local, (gid, gst, gen) = self.heads.segment_batch(f2, vb.f_off, hook)
+        s_off = [0]
+        for n_ in S:
+            s_off.append(s_off[-1] + n_)
+        seg = fxf.SegMeanFn.apply(f2, gid, gst, gen)
+        seg = fxf.gru(self.seg_update, seg, seq_off=s_off, relu=True)     # relu folded into the kernel
+        seg = fxf.linear(seg, self.seg_combine.weight, self.seg_combine.bias)
+        seg_out, seg_cl = self.heads.split(seg)
+        seg_pos = None
+        if fpos is not None:
+            seg_pos = fpos[torch.div(gst + gen, 2, rounding_mode="floor").to(torch.int64)]
+        return dict(S=S, s_off=s_off, local=local, glob=(gid, gst, gen)), seg_out, seg_cl, seg_pos
+
+    def forward_batch(self, f2, a2, fpos, apos, vb):
+        sg, seg_out, seg_cl, seg_pos = self._downsample_batch(f2, fpos, vb)
+        s_off = sg["s_off"]
+        f2a, a2f = self.f2a_layer, self.a2f_layer
+        a, f2a_lg, f2a_at = fxf.x2y(f2a, seg_out, a2, seg_pos if f2a.kq_pos else None, apos if f2a.kq_pos else None,
+                                    rows=(s_off, vb.a_off))
+        a = fxf.decoder(self.action_branch, a, None, query_pos=apos, nvid=vb.nvid)
+        a_out, a_cl = self.heads.split_tokens(a)
+        sgf, a2f_lg, a2f_at = fxf.x2y(a2f, a_out, seg_out, apos if a2f.kq_pos else None,
+                                      seg_pos if a2f.kq_pos else None, rows=(vb.a_off, s_off))
+        # The loss phase's matching starts at one of two points (_VideoBatch.match_before_merge, set by the
+        # model).  Before sf_merge (vn_vloss.BatchMatch): its cost launch and read-back queue ahead of
+        # sf_merge and the frame branch, the host matching overlaps them.  After the frame branch is issued
+        # (vloss.EarlyMatch): its host work runs while the device works through the frame branch, its cost
+        # launch queues behind it.
+        match = vb.on_a2f if vb.last is self else None
+        if match is not None and vb.match_before_merge:
+            match(vb, a_cl, a2f_at, (s_off, sg["local"]))
+        lin = self.sf_merge[0]
+        f = fxf.SegMergeFn.apply(sgf, f2, *sg["glob"], lin.weight, lin.bias)
+        f = _frame_branch_batch(self.frame_branch, f, vb)
+        if match is not None and not vb.match_before_merge:
+            match(vb, a_cl, a2f_at, (s_off, sg["local"]))
+        f_out, f_cl = self.heads.split(f)
+        self._save_batch(vb, sg, f_cl, seg_cl, a_cl, a_out, (f2a_lg, f2a_at, a2f_lg, a2f_at))
+        return f_out, a_out
+
+
+class UpdateBlockTDU(_TDU, Block):
+    """blocks.py:385-497: segment-level update with device-side temporal down/up-sampling."""
+
+    def __init__(self, cfg, nclass):
+        super().__init__()
+        self.cfg = cfg
+        self.nclass = nclass
+        self.heads = ClassHeads(nclass)
+        self._create_update(cfg.BU)
+
+    def _save(self, tdu, frame_clogit, seg_clogit, action_clogit, action_feature):
         self.frame_clogit = frame_clogit
         self.seg_clogit = seg_clogit
         self.tdu = tdu
@@ -348,61 +471,13 @@ class UpdateBlockTDU(Block):
         self.f2a_attn = tdu.attn_seg2frame(self.f2a_layer.attn[0].transpose(2, 1)).transpose(2, 1)
         self.a2f_attn_logit = self.a2f_layer.attn_logit.squeeze(0).unsqueeze(0)
         self.a2f_attn = tdu.attn_seg2frame(self.a2f_layer.attn[0])
-        return frame_feature, action_feature
 
-    def forward_batch(self, f2, a2, fpos, apos, vb):
-        # temporal downsample: one segmentation launch + ONE host read of every video's S
-        # (the first TDU block: the loss phase's label-only host work runs while the host waits for S)
-        hook, vb.while_waiting = vb.while_waiting, None
-        S, local, (gid, gst, gen) = fxf.segments_from_probs_batched(f2, f2.shape[1] - self.nclass, self.nclass,
-                                                                     vb.f_off, hook)
-        s_off = [0]
-        for n_ in S:
-            s_off.append(s_off[-1] + n_)
-        tdus = [basic.TemporalDownsampleUpsample(*local[v]) for v in range(vb.nvid)]
-        seg = fxf.SegMeanFn.apply(f2, gid, gst, gen)
-        seg = fxf.gru(self.seg_update, seg, seq_off=s_off, relu=True)     # relu folded into the kernel
-        seg = fxf.linear(seg, self.seg_combine.weight, self.seg_combine.bias)
-        seg_out, seg_cl = fxf.process_feature(seg, self.nclass)
-        seg_pos = None
-        if fpos is not None:
-            seg_pos = fpos[torch.div(gst + gen, 2, rounding_mode="floor").to(torch.int64)]
-        f2a, a2f = self.f2a_layer, self.a2f_layer
-        a, f2a_lg, f2a_at = fxf.x2y(f2a, seg_out, a2, seg_pos if f2a.kq_pos else None, apos if f2a.kq_pos else None,
-                                    rows=(s_off, vb.a_off))
-        a = fxf.decoder(self.action_branch, a, None, query_pos=apos, nvid=vb.nvid)
-        a_out, a_cl = fxf.process_feature(a, self.nclass + 1)
-        sg, a2f_lg, a2f_at = fxf.x2y(a2f, a_out, seg_out, apos if a2f.kq_pos else None,
-                                     seg_pos if a2f.kq_pos else None, rows=(vb.a_off, s_off))
-        lin = self.sf_merge[0]
-        f = fxf.SegMergeFn.apply(sg, f2, gid, gst, gen, lin.weight, lin.bias)
-        f = _frame_branch_batch(self.frame_branch, f, vb)
-        if vb.on_a2f is not None and vb.last is self:
-            vb.on_a2f(vb, a_cl, a2f_at, (s_off, local))     # (see UpdateBlock.forward_batch)
-        f_out, f_cl = fxf.process_feature(f, self.nclass)
-        n, Q = self.nclass + 1, vb.Q
-        recs = []
-        fc, ac, ao = vb.frames(f_cl), vb.tokens(a_cl), vb.tokens(a_out)
-        sc = torch.split(seg_cl, [s_off[v + 1] - s_off[v] for v in range(vb.nvid)])
-        qs = [Q * S[v] for v in range(vb.nvid)]
-        fat, aat, flg, alg = (torch.split(t, qs) for t in (f2a_at, a2f_at, f2a_lg, a2f_lg))
-        for v in range(vb.nvid):
-            Sv, tdu = S[v], tdus[v]
-            f2a_at_v = fat[v].view(1, 1, Q, Sv)
-            a2f_at_v = aat[v].view(1, 1, Sv, Q)
-            recs.append(dict(frame_clogit=fc[v].unsqueeze(1),
-                             seg_clogit=sc[v].unsqueeze(1), tdu=tdu,
-                             action_clogit=ac[v].unsqueeze(1),
-                             action_feature=ao[v][:, :-n].unsqueeze(1),
-                             f2a_attn_logit=flg[v].view(1, Q, Sv),
-                             f2a_attn=_Lazy(lambda t=tdu, a=f2a_at_v: t.attn_seg2frame(a[0].transpose(2, 1))
-                                            .transpose(2, 1)),
-                             a2f_attn_logit=alg[v].view(1, Sv, Q),
-                             a2f_attn=_Lazy(lambda t=tdu, a=a2f_at_v: t.attn_seg2frame(a[0]))))
-        self.__dict__["_vrec"] = recs     # (plain attributes: no nn.Module.__setattr__ walk)
-        self.__dict__["_bt"] = dict(f_cl=f_cl, a_cl=a_cl, f2a_lg=f2a_lg, a2f_lg=a2f_lg, a2f_at=a2f_at, seg_cl=seg_cl, S=S,
-                        s_off=s_off, local=local)
-        return f_out, a_out
+    def _save_batch(self, vb, sg, f_cl, seg_cl, a_cl, a_out, attn):
+        for rec in _save_views(self, vb, f_cl, a_cl, (a_out, self.nclass + 1), (sg, seg_cl), attn):
+            # the frame-level gathers of the segment attention: only evaluation code reads them
+            tdu, f2a, a2f = rec["tdu"], rec["f2a_attn"], rec["a2f_attn"]
+            rec["f2a_attn"] = _Lazy(lambda t=tdu, a=f2a: t.attn_seg2frame(a.transpose(2, 1)).transpose(2, 1))
+            rec["a2f_attn"] = _Lazy(lambda t=tdu, a=a2f: t.attn_seg2frame(a))
 
     def compute_loss(self, criterion, match=None):
         """blocks.py:487-497: (frame CE + segment CE) / 2 + token CE + segment-level f2a / a2f
@@ -469,9 +544,14 @@ class _FACTBase(nn.Module):
     fact_loss = _lazy_out_attr("fact_loss")
     contrastive_loss = _lazy_out_attr("contrastive_loss")
 
-    def _init_common(self, cfg, n_classes):
+    # Block inputs are marked for factmx.dp (a block's gradient bucket launches once its input has its
+    # gradient); the verb/noun model runs without marks.
+    dp_marks = True
+    # Where the last block starts the loss phase's matching (_TDU.forward_batch).
+    match_before_merge = False
+
+    def _init_common(self, cfg):
         self.cfg = cfg
-        self.num_classes = n_classes
         bcfg = cfg.Bi
         self.frame_pe = basic.PositionalEncoding(bcfg.hid_dim, max_len=10000, empty=(not cfg.FACT.fpos))
         self.channel_masking_dropout = nn.Dropout2d(p=cfg.FACT.cmr)
@@ -479,9 +559,22 @@ class _FACTBase(nn.Module):
             self.action_query = nn.Parameter(torch.randn([cfg.FACT.ntoken, 1, bcfg.a_dim]))
         else:
             self.action_pe = basic.PositionalEncoding(bcfg.a_dim, max_len=1000)
-            self.action_embed = nn.Embedding(n_classes, bcfg.a_dim)
+            self._create_embed(bcfg.a_dim)
 
-    def _run_blocks(self, seq, transcript):
+    def _create_embed(self, a_dim):
+        self.action_embed = nn.Embedding(self.num_classes, a_dim)
+
+    def _transcript_tokens(self, transcript):
+        """(token feature, token position) of a transcript input."""
+        action_pe = self.action_pe(transcript)
+        return self.action_embed(transcript).unsqueeze(1) + action_pe, torch.zeros_like(action_pe)
+
+    def _mark(self, k, block, frame_feature):
+        if self.dp_marks:
+            mark_block_input(self, k, frame_feature)
+            block.__dict__["_dp_ctx"] = (self, k)      # (not a submodule registration)
+
+    def _run_blocks(self, seq, transcript=None):
         frame_feature = seq
         frame_pe = _frame_pos(self.frame_pe, seq)
         if self.cfg.FACT.cmr and self.training:
@@ -493,25 +586,29 @@ class _FACTBase(nn.Module):
             action_pe = self.action_query
             action_feature = torch.zeros_like(action_pe)
         else:
-            action_pe = self.action_pe(transcript)
-            action_feature = self.action_embed(transcript).unsqueeze(1) + action_pe
-            action_pe = torch.zeros_like(action_pe)
+            action_feature, action_pe = self._transcript_tokens(transcript)
         block_output = []
         for k, block in enumerate(self.block_list):
-            mark_block_input(self, k, frame_feature)
-            block.__dict__["_dp_ctx"] = (self, k)      # (not a submodule registration)
+            self._mark(k, block, frame_feature)
             frame_feature, action_feature = block(frame_feature, action_feature, frame_pe, action_pe)
             block_output.append([frame_feature, action_feature])
         return block_output
 
+    _forward_one_video = _run_blocks
+
+    def _head_batch(self, f2, vb):
+        """A model-level head on the last block's stacked frame rows: None, or its restore(v)."""
+        return None
+
     def _forward_batch(self, seq_list, on_a2f=None):
         """All videos through the blocks in lockstep (see _forward_videos); returns restore(v), which
-        points every side-channel attribute at video v's views.  ``on_a2f`` (vloss.EarlyMatch) runs
-        when the last block's token logits and token->frame attention exist."""
+        points every side-channel attribute at video v's views.  ``on_a2f`` (vloss.EarlyMatch,
+        vn_vloss.BatchMatch) runs when the last block's token logits and token -> frame (segment)
+        attention exist."""
         nvid = len(seq_list)
         Q = self.cfg.FACT.ntoken
         vb = _VideoBatch(nvid, [int(s.shape[0]) for s in seq_list], Q)
-        vb.on_a2f, vb.last = on_a2f, self.block_list[-1]
+        vb.on_a2f, vb.last, vb.match_before_merge = on_a2f, self.block_list[-1], self.match_before_merge
         if on_a2f is not None:
             dev = seq_list[0].device
             vb.while_waiting = lambda: on_a2f.prepare(dev)
@@ -530,23 +627,16 @@ class _FACTBase(nn.Module):
         apos = fxf.pos_sink(self.action_query.squeeze(1).repeat(nvid, 1))
         a2 = torch.zeros_like(apos)
         for k, blk in enumerate(self.block_list):
-            mark_block_input(self, k, f2)       # DP: block k's gradient bucket launches once f2 has its grad
-            blk.__dict__["_dp_ctx"] = (self, k)
+            self._mark(k, blk, f2)
             f2, a2 = blk.forward_batch(f2, a2, fpos, apos, vb)
-        proj = None
-        if isinstance(self, FACT_CLIP):
-            feat_dim = f2.shape[-1] - self.num_classes
-            proj = self.frame_projection(f2[:, :feat_dim])
-
-        self._proj = proj
+        head = self._head_batch(f2, vb)
         self._vb = vb
-        proj_v = None if proj is None else vb.frames(proj)
 
         def restore(v):
             for blk in self.block_list:
                 _set_side(blk, blk._vrec[v])
-            if proj_v is not None:
-                self.projected_frame_embeddings = proj_v[v].unsqueeze(1)
+            if head is not None:
+                head(v)
         return restore
 
     def _fact_loss(self, label, label_host=None):
@@ -566,12 +656,10 @@ class FACT(_FACTBase):
 
     def __init__(self, cfg, in_dim, n_classes):
         super().__init__()
-        self._init_common(cfg, n_classes)
+        self.num_classes = n_classes
+        self._init_common(cfg)
         self.block_list = _build_blocks(cfg, in_dim, n_classes)
         self.mcriterion = None
-
-    def _forward_one_video(self, seq, transcript=None):
-        return self._run_blocks(seq, transcript)
 
     def _loss_one_video(self, label, label_host=None):
         return self._fact_loss(label, label_host)
@@ -589,7 +677,8 @@ class FACT_CLIP(_FACTBase):
 
     def __init__(self, cfg, in_dim, n_classes, text_embeddings=None):
         super().__init__()
-        self._init_common(cfg, n_classes)
+        self.num_classes = n_classes
+        self._init_common(cfg)
         # feature width from Bi.hid_dim, evaluated before the block loop (blocks.py:568)
         frame_feature_dim = cfg.Bi.hid_dim - n_classes
         self.frame_projection = FeatureProjection(feature_dim=frame_feature_dim, clip_dim=512,
@@ -608,6 +697,15 @@ class FACT_CLIP(_FACTBase):
         feat_dim = frame_feature.shape[-1] - self.num_classes
         self.projected_frame_embeddings = self.frame_projection(frame_feature[:, :, :feat_dim])
         return out
+
+    def _head_batch(self, f2, vb):
+        feat_dim = f2.shape[-1] - self.num_classes
+        self._proj = self.frame_projection(f2[:, :feat_dim])
+        proj_v = vb.frames(self._proj)
+
+        def restore(v):
+            self.projected_frame_embeddings = proj_v[v].unsqueeze(1)
+        return restore
 
     def _loss_one_video(self, label, label_host=None):
         fact_loss = self._fact_loss(label, label_host)
@@ -694,7 +792,10 @@ class _VideoBatch:
         for T in self.Ts:
             self.f_off.append(self.f_off[-1] + T)
         self.a_off = [v * Q for v in range(nvid + 1)]
+        # the loss phase's hooks (set by the model): on_a2f(vb, token logits, a2f attention[, segments]) runs in
+        # block ``last``, before sf_merge or after the frame branch is issued (_TDU.forward_batch)
         self.on_a2f = self.last = self.while_waiting = None
+        self.match_before_merge = False
 
     def fr(self, v):
         return slice(self.f_off[v], self.f_off[v + 1])

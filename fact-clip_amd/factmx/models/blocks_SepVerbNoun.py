@@ -19,6 +19,14 @@ batch of CUDA videos (any lengths, at most blocks.MAX_LOCKSTEP_VIDEOS, no ``cfg.
 every block over the stacked videos (``forward_batch``), with one matching-cost launch, one term table,
 one prediction pass and one read-back per step (vn_vloss.run_batch); the side-channel attributes then hold
 the last video's views, as in models.blocks.
+
+This file holds what is particular to the verb/noun heads: the mapping, ``VerbNounHeads`` (the class
+columns and the segmentation, as blocks.ClassHeads), ``Block`` (action log-probabilities, loss helpers,
+prediction, the lazy ``frame_logp`` / ``seg_logp`` and the side channels ``_save_logp`` / ``_save_attn`` /
+``_save_batch``), the input block, the transcript embedding and the ``forward`` drivers with their read-back.
+The branch constructors (blocks.Block), the segment-level flow of both blocks for one video and for stacked
+videos (blocks._TDU), the per-video views (blocks._save_views) and the model's walk through the blocks
+(blocks._FACTBase._run_blocks / _forward_batch) are shared with models.blocks.
 """
 import torch
 import torch.nn as nn
@@ -30,8 +38,8 @@ from . import blocks
 from . import loss
 from . import vloss
 from . import vn_vloss
-from .basic import time_mask, torch_class_label_to_segment_label
-from .blocks import _frame_branch_batch, _frame_pos, _Lazy, _lazy_attr, _set_side, _VideoBatch
+from .basic import torch_class_label_to_segment_label
+from .blocks import _frame_branch_batch, _Lazy, _lazy_attr
 from .loss import MatchCriterion
 
 _VNMAP = None     # the installed mapping (reference: _VIDS / _NIDS)
@@ -98,8 +106,14 @@ def _lockstep_ok(net, seq_list):
     return all(basic._fused_decoder_ok(blk.action_branch) for blk in net.block_list)
 
 
-class FACT(nn.Module):
-    """blocks_SepVerbNoun.py:14-142."""
+class FACT(blocks._FACTBase):
+    """blocks_SepVerbNoun.py:14-142.  The blocks run through the base's ``_run_blocks`` (one video) and
+    ``_forward_batch`` (lockstep)."""
+
+    dp_marks = False              # no factmx.dp marks on this model's block inputs
+    # the last block starts the matching (vn_vloss.BatchMatch) before sf_merge: its cost launch and read-back
+    # queue ahead of sf_merge and the frame branch, the host matching overlaps them
+    match_before_merge = True
 
     def __init__(self, cfg, in_dim, n_classes1=98, n_classes2=301):
         super().__init__()
@@ -108,18 +122,10 @@ class FACT(nn.Module):
         if (n_classes1, n_classes2) != (self.vnmap.num_verbs, self.vnmap.num_nouns):
             raise ValueError(f"{n_classes1} verb / {n_classes2} noun classes, but the installed mapping has "
                              f"{self.vnmap.num_verbs} / {self.vnmap.num_nouns}")
-        self.cfg = cfg
         self.num_classes1 = n_classes1   # verbs
         self.num_classes2 = n_classes2   # nouns
+        self._init_common(cfg)
         base_cfg = cfg.Bi
-        self.frame_pe = basic.PositionalEncoding(base_cfg.hid_dim, max_len=10000, empty=(not cfg.FACT.fpos))
-        self.channel_masking_dropout = nn.Dropout2d(p=cfg.FACT.cmr)
-        if not cfg.FACT.trans:
-            self.action_query = nn.Parameter(torch.randn([cfg.FACT.ntoken, 1, base_cfg.a_dim]))
-        else:
-            self.action_pe = basic.PositionalEncoding(base_cfg.a_dim, max_len=1000)
-            self.verb_embed = nn.Embedding(n_classes1, base_cfg.a_dim // 2)
-            self.noun_embed = nn.Embedding(n_classes2, base_cfg.a_dim // 2)
         block_list = []
         for t in cfg.FACT.block:
             if t == "I":
@@ -134,29 +140,16 @@ class FACT(nn.Module):
         self.block_list = nn.ModuleList(block_list)
         self.mcriterion = None
 
-    def _forward_one_video(self, seq, transcript=None):
-        frame_feature = seq
-        frame_pe = _frame_pos(self.frame_pe, seq)
-        if self.cfg.FACT.cmr and self.training:
-            frame_feature = self.channel_masking_dropout(frame_feature.permute([1, 2, 0])).permute([2, 0, 1])
-        if self.cfg.TM.use and self.training:
-            frame_feature = time_mask(frame_feature, self.cfg.TM.t, self.cfg.TM.m, self.cfg.TM.p,
-                                      replace_with_zero=True)
-        if not self.cfg.FACT.trans:
-            action_pe = self.action_query
-            action_feature = torch.zeros_like(action_pe)
-        else:
-            vtranscript, ntranscript = self.vnmap.verb_noun_of(transcript)
-            action_pe = self.action_pe(transcript)
-            vfeature = self.verb_embed(vtranscript).unsqueeze(1)
-            nfeature = self.noun_embed(ntranscript).unsqueeze(1)
-            action_feature = torch.cat([vfeature, nfeature], dim=-1) + action_pe
-            action_pe = torch.zeros_like(action_pe)
-        block_output = []
-        for block in self.block_list:
-            frame_feature, action_feature = block(frame_feature, action_feature, frame_pe, action_pe)
-            block_output.append((frame_feature, action_feature))
-        return block_output
+    def _create_embed(self, a_dim):
+        self.verb_embed = nn.Embedding(self.num_classes1, a_dim // 2)
+        self.noun_embed = nn.Embedding(self.num_classes2, a_dim // 2)
+
+    def _transcript_tokens(self, transcript):
+        vtranscript, ntranscript = self.vnmap.verb_noun_of(transcript)
+        action_pe = self.action_pe(transcript)
+        vfeature = self.verb_embed(vtranscript).unsqueeze(1)
+        nfeature = self.noun_embed(ntranscript).unsqueeze(1)
+        return torch.cat([vfeature, nfeature], dim=-1) + action_pe, torch.zeros_like(action_pe)
 
     def _loss_one_video(self, label):
         mcriterion: MatchCriterion = self.mcriterion
@@ -172,39 +165,6 @@ class FACT(nn.Module):
             match = mcriterion.match(torch.exp(block.action_logp), block.a2f_attn)
         self.loss_list = [blk.compute_loss(mcriterion, match) for blk in self.block_list]
         return sum(self.loss_list) / len(self.loss_list)
-
-    def _forward_batch(self, seq_list, on_a2f=None):
-        """All videos through the blocks in lockstep, as blocks._FACTBase._forward_batch; returns
-        restore(v), which points every side-channel attribute at video v's views.  ``on_a2f``
-        (vn_vloss.BatchMatch) runs when the last block's token logits and token -> segment attention exist."""
-        nvid = len(seq_list)
-        vb = _VideoBatch(nvid, [int(s.shape[0]) for s in seq_list], self.cfg.FACT.ntoken)
-        vb.on_a2f, vb.last = on_a2f, self.block_list[-1]
-        if on_a2f is not None:
-            dev = seq_list[0].device
-            vb.while_waiting = lambda: on_a2f.prepare(dev)
-        frames = []
-        for seq in seq_list:
-            x = seq.unsqueeze(1)
-            if self.cfg.FACT.cmr and self.training:
-                x = self.channel_masking_dropout(x.permute([1, 2, 0])).permute([2, 0, 1])
-            if self.cfg.TM.use and self.training:
-                x = time_mask(x, self.cfg.TM.t, self.cfg.TM.m, self.cfg.TM.p, replace_with_zero=True)
-            frames.append(x.squeeze(1))
-        f2 = torch.cat(frames, 0)
-        fpe = [_frame_pos(self.frame_pe, s.unsqueeze(1)) for s in seq_list]
-        fpos = None if fpe[0] is None else torch.cat([p.squeeze(1) for p in fpe], 0)
-        # one shared gradient buffer for the query table's readers (fxf.PosGradSink: no pairwise adds)
-        apos = fxf.pos_sink(self.action_query.squeeze(1).repeat(nvid, 1))
-        a2 = torch.zeros_like(apos)
-        for blk in self.block_list:
-            f2, a2 = blk.forward_batch(f2, a2, fpos, apos, vb)
-        self._vb = vb
-
-        def restore(v):
-            for blk in self.block_list:
-                _set_side(blk, blk._vrec[v])
-        return restore
 
     def _forward_lockstep(self, seq_list, label_list, compute_loss):
         """``forward`` for a batch ``_lockstep_ok`` accepts.  A batch in which a video's match exceeds
@@ -265,23 +225,44 @@ class FACT(nn.Module):
             return sum(final_loss) / len(final_loss), save_list
         return save_list
 
-    def save_model(self, fname):
-        torch.save(self.state_dict(), fname)
+
+class VerbNounHeads:
+    """blocks.ClassHeads for n1 verb + n2 noun class columns, each group with its own softmax (token rows:
+    one null column more per group); frames are segmented by the argmax over the mapped actions."""
+
+    def __init__(self, nclass1, nclass2, vnmap):
+        self.n1, self.n2, self.vnmap = nclass1, nclass2, vnmap
+
+    def split(self, x):
+        return fxf.process_feature(x, self.n1 + self.n2, class_sep=self.n1)
+
+    def split_tokens(self, x):
+        return fxf.process_feature(x, self.n1 + self.n2 + 2, class_sep=self.n1 + 1)
+
+    def segment(self, f2):
+        n1, n2 = self.n1, self.n2
+        return basic.TemporalDownsampleUpsample.from_vn_probs(f2, f2.shape[1] - n1 - n2, n1, n2, self.vnmap)
+
+    def segment_batch(self, f2, f_off, hook):
+        n1, n2 = self.n1, self.n2
+        return fxf.segments_from_vn_probs_batched(f2, f2.shape[1] - n1 - n2, n1, n2, self.vnmap, f_off, hook)
 
 
-class Block(nn.Module):
-    """blocks_SepVerbNoun.py:177-355."""
+class Block(blocks.Block):
+    """blocks_SepVerbNoun.py:177-355: the verb/noun heads on the shared branches (``create_*``) and
+    side-channel plumbing of blocks.Block.  ``a2f_attn`` / ``f2a_attn`` (lazy there too) are the frame-level
+    gathers of the segment attention rows (``a2f_seg_attn`` / ``f2a_seg_attn``, (1, S, Q))."""
 
     # side-channel tables nothing on the fused path reads: built on first read
     frame_logp = _lazy_attr("frame_logp")
     seg_logp = _lazy_attr("seg_logp")
-    # frame-level gathers of the segment attention rows (a2f_seg_attn / f2a_seg_attn, (1, S, Q))
-    a2f_attn = _lazy_attr("a2f_attn")
-    f2a_attn = _lazy_attr("f2a_attn")
 
-    def __repr__(self):
-        return (f"{type(self).__name__}(\n  f:{self.frame_branch},\n  a:{self.action_branch},\n"
-                f"  a2f:{getattr(self, 'a2f_layer', None)},\n  f2a:{getattr(self, 'f2a_layer', None)}\n)")
+    def _init_heads(self, cfg, nclass1, nclass2, vnmap):
+        self.cfg = cfg
+        self.nclass1 = nclass1
+        self.nclass2 = nclass2
+        self.vnmap = vnmap
+        self.heads = VerbNounHeads(nclass1, nclass2, vnmap)
 
     def combine_verb_noun_to_action(self, clogit, action=False, apply_log=True):
         """Action log-probabilities (T, 1, A (+ 1 null column)) of verb/noun class logits (T, 1, n1 + n2)."""
@@ -292,37 +273,6 @@ class Block(nn.Module):
     def process_feature(self, feature, nclass1, nclass2):
         out, clogit = fxf.process_feature(feature, nclass1 + nclass2, class_sep=nclass1)
         return out.unsqueeze(1), clogit.unsqueeze(1)
-
-    def create_fbranch(self, cfg, in_dim=None, f_inmap=False):
-        if in_dim is None:
-            in_dim = cfg.f_dim
-        if cfg.f == "m":
-            return basic.MSTCN(in_dim, cfg.f_dim, cfg.hid_dim, cfg.f_layers, dropout=cfg.dropout, ln=cfg.f_ln,
-                               ngroup=cfg.f_ngp, in_map=f_inmap)
-        if cfg.f == "m2":
-            return basic.MSTCN2(in_dim, cfg.f_dim, cfg.hid_dim, cfg.f_layers, dropout=cfg.dropout, ln=cfg.f_ln,
-                                ngroup=cfg.f_ngp, in_map=f_inmap)
-        raise ValueError(f"frame branch type {cfg.f!r} (the reference builds only 'm' / 'm2')")
-
-    def create_abranch(self, cfg):
-        if cfg.a == "sa":
-            layer = basic.SALayer(cfg.a_dim, cfg.a_nhead, dim_feedforward=cfg.a_ffdim, dropout=cfg.dropout,
-                                  attn_dropout=cfg.dropout)
-            return basic.SADecoder(cfg.a_dim, cfg.a_dim, cfg.hid_dim, layer, cfg.a_layers, in_map=False)
-        if cfg.a == "sca":
-            layer = basic.SCALayer(cfg.a_dim, cfg.hid_dim, cfg.a_nhead, cfg.a_ffdim, dropout=cfg.dropout,
-                                   attn_dropout=cfg.dropout)
-            norm = torch.nn.LayerNorm(cfg.a_dim)
-            return basic.SCADecoder(cfg.a_dim, cfg.a_dim, cfg.hid_dim, layer, cfg.a_layers, norm=norm, in_map=False)
-        if cfg.a in ("gru", "gru_om"):
-            assert self.cfg.FACT.trans
-            return basic.ActionUpdate_GRU(cfg.a_dim, cfg.a_dim, cfg.hid_dim, cfg.a_layers, dropout=cfg.dropout,
-                                          out_map=(cfg.a == "gru_om"))
-        raise ValueError(cfg.a)
-
-    def create_cross_attention(self, cfg, outdim, kq_pos=True):
-        return basic.X2Y_map(cfg.hid_dim, cfg.hid_dim, outdim, head_dim=cfg.hid_dim, dropout=cfg.dropout,
-                             kq_pos=kq_pos)
 
     def action_token_loss(self, criterion: MatchCriterion, match, action_logp):
         """blocks_SepVerbNoun.py:271-283: weighted one-hot NLL of the token log-probabilities, mean
@@ -336,76 +286,29 @@ class Block(nn.Module):
         clabel[aind, criterion.transcript[sind]] = 1
         return ((-logp * clabel) * criterion.cweight).sum(-1).mean()
 
-    def temporal_downsample(self, frame_feature):
-        n1, n2 = self.nclass1, self.nclass2
-        f2 = fxf._2d(frame_feature)
-        tdu = basic.TemporalDownsampleUpsample.from_vn_probs(f2, f2.shape[1] - n1 - n2, n1, n2, self.vnmap)
-        seg = tdu.feature_frame2seg(frame_feature)
-        seg = fxf.gru(self.seg_update, seg, relu=True)            # relu(seg_update(seg))
-        seg = fxf.linear(seg, self.seg_combine.weight, self.seg_combine.bias).unsqueeze(1)
-        seg, seg_clogit = self.process_feature(seg, n1, n2)
-        return tdu, seg, seg_clogit
-
-    def temporal_upsample(self, tdu, seg_feature, frame_feature):
-        lin = self.sf_merge[0]
-        y = fxf.SegMergeFn.apply(fxf._2d(seg_feature), fxf._2d(frame_feature), tdu.seg_id32, tdu.start32, tdu.end32,
-                                 lin.weight, lin.bias)
-        return y.unsqueeze(1)
-
-    def _downsample_batch(self, f2, fpos, vb):
-        """``temporal_downsample`` over the stacked videos: one segmentation launch + ONE host read of every
-        video's S (the first block: the loss phase's label-only host work runs while the host waits),
-        segment means on the global tables, the BiGRU over the ragged segment rows.  Returns the segment
-        record and (seg feature, seg class logits, seg positions)."""
-        n1, n2 = self.nclass1, self.nclass2
-        hook, vb.while_waiting = vb.while_waiting, None
-        S, local, (gid, gst, gen) = fxf.segments_from_vn_probs_batched(f2, f2.shape[1] - n1 - n2, n1, n2, self.vnmap,
-                                                                        vb.f_off, hook)
-        s_off = [0]
-        for n_ in S:
-            s_off.append(s_off[-1] + n_)
-        seg = fxf.SegMeanFn.apply(f2, gid, gst, gen)
-        seg = fxf.gru(self.seg_update, seg, seq_off=s_off, relu=True)     # relu(seg_update(seg))
-        seg = fxf.linear(seg, self.seg_combine.weight, self.seg_combine.bias)
-        seg_out, seg_cl = fxf.process_feature(seg, n1 + n2, class_sep=n1)
-        seg_pos = None
-        if fpos is not None:
-            seg_pos = fpos[torch.div(gst + gen, 2, rounding_mode="floor").to(torch.int64)]
-        return dict(S=S, s_off=s_off, local=local, glob=(gid, gst, gen)), seg_out, seg_cl, seg_pos
-
-    def _save_batch(self, vb, sg, f_cl, seg_cl, a_cl, attn=None):
-        """Per-video side channels of the stacked outputs as views through one split node per tensor
-        (``_vrec``: what ``_save_logp`` / ``_save_attn`` set for one video), and the stacked tensors the
-        loss phase reads (``_bt``)."""
-        Q, S, nvid = vb.Q, sg["S"], vb.nvid
-        fc, ac, sc = vb.frames(f_cl), vb.tokens(a_cl), torch.split(seg_cl, S)
+    def _save_batch(self, vb, sg, f_cl, seg_cl, a_cl, a_out=None, attn=None):
+        """Per-video side channels of the stacked outputs (``_vrec``: what ``_save_logp`` / ``_save_attn``
+        set for one video, on the views of blocks._save_views) and the stacked tensors the loss phase reads
+        (``_bt``)."""
+        views = blocks._save_views(self, vb, f_cl, a_cl, seg=(sg, seg_cl), attn=attn)
         alp = vb.tokens(fxf.verb_noun_logp(a_cl, self.vnmap, action=True))
-        tdus = [basic.TemporalDownsampleUpsample(*sg["local"][v]) for v in range(nvid)]
-        bt = dict(f_cl=f_cl, seg_cl=seg_cl, a_cl=a_cl, S=S, s_off=sg["s_off"], local=sg["local"])
-        if attn is not None:
-            f2a_lg, f2a_at, a2f_lg, a2f_at = attn
-            qs = [Q * n_ for n_ in S]
-            fat, aat, flg, alg = (torch.split(t, qs) for t in (f2a_at, a2f_at, f2a_lg, a2f_lg))
-            bt.update(f2a_lg=f2a_lg, a2f_lg=a2f_lg, a2f_at=a2f_at)
         recs = []
-        for v in range(nvid):
-            fcv, scv, tdu = fc[v].unsqueeze(1), sc[v].unsqueeze(1), tdus[v]
-            rec = dict(_fused=True, _clogits=(fcv, scv, ac[v].unsqueeze(1)), tdu=tdu,
+        for v, w in enumerate(views):
+            fcv, scv, tdu = w["frame_clogit"], w["seg_clogit"], w["tdu"]
+            rec = dict(_fused=True, _clogits=(fcv, scv, w["action_clogit"]), tdu=tdu,
                        seg_logp=_Lazy(lambda c=scv: self.combine_verb_noun_to_action(c)),
                        frame_logp=_Lazy(lambda c=fcv: self.combine_verb_noun_to_action(c)),
                        action_logp=alp[v].unsqueeze(1))
             if attn is None:
                 rec.update(f2a_seg_attn=None, a2f_seg_attn=None, f2a_attn=None, a2f_attn=None)
             else:
-                Sv = S[v]
-                f2a_seg, a2f_seg = fat[v].view(1, Q, Sv).transpose(2, 1), aat[v].view(1, Sv, Q)
+                f2a_seg, a2f_seg = w["f2a_attn"].transpose(2, 1), w["a2f_attn"]
                 rec.update(f2a_seg_attn=f2a_seg, a2f_seg_attn=a2f_seg,
                            f2a_attn=_Lazy(lambda t=tdu, a=f2a_seg: t.attn_seg2frame(a).transpose(2, 1)),
                            a2f_attn=_Lazy(lambda t=tdu, a=a2f_seg: t.attn_seg2frame(a)),
-                           f2a_attn_logit=flg[v].view(1, Q, Sv), a2f_attn_logit=alg[v].view(1, Sv, Q))
+                           f2a_attn_logit=w["f2a_attn_logit"], a2f_attn_logit=w["a2f_attn_logit"])
             recs.append(rec)
         self.__dict__["_vrec"] = recs     # (plain attributes: no nn.Module.__setattr__ walk)
-        self.__dict__["_bt"] = bt
 
     def _save_logp(self, frame_clogit, seg_clogit, action_clogit, tdu):
         self._fused = FUSED_LOSS and frame_clogit.is_cuda
@@ -476,28 +379,25 @@ class Block(nn.Module):
         return self._eval_w_transcript(transcript, self.a2f_attn)
 
 
-class InputBlockTDU(Block):
-    """blocks_SepVerbNoun.py:358-413."""
+class InputBlockTDU(blocks._TDU, Block):
+    """blocks_SepVerbNoun.py:358-413: the input block reads the segments of its own frame branch (the
+    down-sampling half of blocks._TDU)."""
 
     def __init__(self, cfg, in_dim, nclass1, nclass2, vnmap):
         super().__init__()
-        self.cfg = cfg
-        self.nclass1 = nclass1
-        self.nclass2 = nclass2
-        self.vnmap = vnmap
+        self._init_heads(cfg, nclass1, nclass2, vnmap)
         bcfg = cfg.Bi
         self.frame_branch = self.create_fbranch(bcfg, in_dim, f_inmap=True)
         self.action_branch = self.create_abranch(bcfg)
-        self.seg_update = nn.GRU(bcfg.hid_dim, bcfg.hid_dim // 2, 2, bidirectional=True)
-        self.seg_combine = nn.Linear(bcfg.hid_dim, bcfg.hid_dim)
+        self._create_seg(bcfg, 2)
 
     def forward(self, frame_feature, action_feature, frame_pos, action_pos):
         frame_feature = self.frame_branch(frame_feature)
-        frame_feature, frame_clogit = self.process_feature(frame_feature, self.nclass1, self.nclass2)
+        frame_feature, frame_clogit = self._split(frame_feature)
         tdu, seg_feature, seg_clogit = self.temporal_downsample(frame_feature)
         seg_pos = None if frame_pos is None else frame_pos[tdu.centers()]
         action_feature = self.action_branch(action_feature, seg_feature, pos=seg_pos, query_pos=action_pos)
-        action_feature, action_clogit = self.process_feature(action_feature, self.nclass1 + 1, self.nclass2 + 1)
+        action_feature, action_clogit = self._split(action_feature, tokens=True)
         self._save_logp(frame_clogit, seg_clogit, action_clogit, tdu)
         self._save_attn(None, None, None)
         return frame_feature, action_feature
@@ -505,13 +405,12 @@ class InputBlockTDU(Block):
     def forward_batch(self, f2, a2, fpos, apos, vb):
         """``forward`` over vb.nvid stacked videos (frames (sum T, C), tokens (nvid * Q, A)): the SCA decoder
         reads each video's segment rows through the ragged memory offsets."""
-        n1, n2 = self.nclass1, self.nclass2
         f = _frame_branch_batch(self.frame_branch, f2, vb)
-        f_out, f_cl = fxf.process_feature(f, n1 + n2, class_sep=n1)
+        f_out, f_cl = self.heads.split(f)
         sg, seg_out, seg_cl, seg_pos = self._downsample_batch(f_out, fpos, vb)
         a = fxf.decoder(self.action_branch, a2, seg_out, pos=seg_pos, query_pos=apos, nvid=vb.nvid,
                         mem_off=sg["s_off"])
-        a_out, a_cl = fxf.process_feature(a, n1 + n2 + 2, class_sep=n1 + 1)
+        a_out, a_cl = self.heads.split_tokens(a)
         self._save_batch(vb, sg, f_cl, seg_cl, a_cl)
         return f_out, a_out
 
@@ -520,62 +419,20 @@ class InputBlockTDU(Block):
         return self._frame_seg_loss(criterion) + atk_loss
 
 
-class UpdateBlockTDU(Block):
-    """blocks_SepVerbNoun.py:415-496: segment-level update with temporal down/up-sampling."""
+class UpdateBlockTDU(blocks._TDU, Block):
+    """blocks_SepVerbNoun.py:415-496: segment-level update with temporal down/up-sampling (the flow is
+    blocks._TDU's ``forward`` / ``forward_batch``)."""
 
     def __init__(self, cfg, nclass1, nclass2, vnmap):
         super().__init__()
-        self.cfg = cfg
-        self.nclass1 = nclass1
-        self.nclass2 = nclass2
-        self.vnmap = vnmap
-        bcfg = cfg.BU
-        self.frame_branch = self.create_fbranch(bcfg)
-        self.seg_update = nn.GRU(bcfg.hid_dim, bcfg.hid_dim // 2, bcfg.s_layers, bidirectional=True)
-        self.seg_combine = nn.Linear(bcfg.hid_dim, bcfg.hid_dim)
-        self.f2a_layer = self.create_cross_attention(bcfg, bcfg.a_dim)
-        self.action_branch = self.create_abranch(bcfg)
-        self.a2f_layer = self.create_cross_attention(bcfg, bcfg.f_dim)
-        self.sf_merge = nn.Sequential(nn.Linear(bcfg.hid_dim + bcfg.f_dim, bcfg.f_dim), nn.ReLU())
+        self._init_heads(cfg, nclass1, nclass2, vnmap)
+        self._create_update(cfg.BU)
 
-    def forward(self, frame_feature, action_feature, frame_pos, action_pos):
-        tdu, seg_feature, seg_clogit = self.temporal_downsample(frame_feature)
-        seg_pos = None if frame_pos is None else frame_pos[tdu.centers()]
-        action_feature = self.f2a_layer(seg_feature, action_feature, X_pos=seg_pos, Y_pos=action_pos)
-        action_feature = self.action_branch(action_feature, action_pos)
-        action_feature, action_clogit = self.process_feature(action_feature, self.nclass1 + 1, self.nclass2 + 1)
-        seg_feature = self.a2f_layer(action_feature, seg_feature, X_pos=action_pos, Y_pos=seg_pos)
-        frame_feature = self.temporal_upsample(tdu, seg_feature, frame_feature)
-        frame_feature = self.frame_branch(frame_feature)
-        frame_feature, frame_clogit = self.process_feature(frame_feature, self.nclass1, self.nclass2)
+    def _save(self, tdu, frame_clogit, seg_clogit, action_clogit, action_feature):
         self._save_logp(frame_clogit, seg_clogit, action_clogit, tdu)
         self.f2a_attn_logit = self.f2a_layer.attn_logit.squeeze(0).unsqueeze(0)
         self.a2f_attn_logit = self.a2f_layer.attn_logit.squeeze(0).unsqueeze(0)
         self._save_attn(tdu, self.f2a_layer.attn[0].transpose(2, 1), self.a2f_layer.attn[0])
-        return frame_feature, action_feature
-
-    def forward_batch(self, f2, a2, fpos, apos, vb):
-        n1, n2 = self.nclass1, self.nclass2
-        sg, seg_out, seg_cl, seg_pos = self._downsample_batch(f2, fpos, vb)
-        s_off = sg["s_off"]
-        f2a, a2f = self.f2a_layer, self.a2f_layer
-        a, f2a_lg, f2a_at = fxf.x2y(f2a, seg_out, a2, seg_pos if f2a.kq_pos else None, apos if f2a.kq_pos else None,
-                                    rows=(s_off, vb.a_off))
-        a = fxf.decoder(self.action_branch, a, None, query_pos=apos, nvid=vb.nvid)
-        a_out, a_cl = fxf.process_feature(a, n1 + n2 + 2, class_sep=n1 + 1)
-        sgf, a2f_lg, a2f_at = fxf.x2y(a2f, a_out, seg_out, apos if a2f.kq_pos else None,
-                                      seg_pos if a2f.kq_pos else None, rows=(vb.a_off, s_off))
-        if vb.on_a2f is not None and vb.last is self:
-            # the loss phase's matching starts here (vn_vloss.BatchMatch): its cost launch and read-back
-            # queue ahead of sf_merge and the frame branch, the host matching overlaps them
-            vb.on_a2f(vb, a_cl, a2f_at, (s_off, sg["local"]))
-        gid, gst, gen = sg["glob"]
-        lin = self.sf_merge[0]
-        f = fxf.SegMergeFn.apply(sgf, f2, gid, gst, gen, lin.weight, lin.bias)
-        f = _frame_branch_batch(self.frame_branch, f, vb)
-        f_out, f_cl = fxf.process_feature(f, n1 + n2, class_sep=n1)
-        self._save_batch(vb, sg, f_cl, seg_cl, a_cl, (f2a_lg, f2a_at, a2f_lg, a2f_at))
-        return f_out, a_out
 
     def compute_loss(self, criterion: MatchCriterion, match=None):
         atk_loss = self._token_loss(criterion, match) / 2

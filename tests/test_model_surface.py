@@ -61,6 +61,21 @@ def test_block_layout_follows_config():
     assert net.action_query.shape == (meta["FACT"]["ntoken"], 1, meta["Bi"]["a_dim"])
 
 
+@pytest.mark.parametrize("name", ["tiny_vn", "tiny_vn_o2m", "tiny_vn_batch"])
+def test_verb_noun_model_surface(name):
+    # the verb/noun FACT shares its branch constructors and segment-level sub-modules with models.blocks:
+    # creation order (seeded initialisation, reference checkpoints), buffers and block kinds stay its own
+    from factmx.models import blocks_SepVerbNoun as vn
+    fx = load_fixture(name)
+    meta = tiny_meta(fx)
+    vn.set_verb_noun_ids(fx["vids"].tolist(), fx["nids"].tolist())
+    net = vn.FACT(cfg_from_meta(meta), meta["D"], meta["V"], meta["N"])
+    got = [(n, list(p.shape)) for n, p in net.named_parameters()]
+    assert got == [(n, list(s)) for n, s in meta["param_shapes"].items()]
+    assert {n for n, _ in net.named_buffers()} == {"frame_pe.pe"}
+    assert [type(b).__name__ for b in net.block_list] == ["InputBlockTDU", "UpdateBlockTDU", "UpdateBlockTDU"]
+
+
 def test_dropout_seed_follows_torch_manual_seed():
     # training dropout inside the fused kernels draws one seed per site from torch's CPU generator:
     # torch.manual_seed fixes the masks as it fixes nn.Dropout's
