@@ -18,6 +18,7 @@
 //                     ground-truth segments, computed in the kernels.
 //   fx_loss_terms_bwd the gradient of every term's logits: class, attention, InfoNCE launches (+ GEMM).
 //   fx_eval_pred      one launch: every video's per-frame prediction (eval_with_clip / Block._eval).
+//   fx_eval_pred_trans  the same for a transcript-conditioned model (Block._eval_w_transcript).
 #include <algorithm>
 #include <cmath>
 
@@ -594,6 +595,45 @@ __global__ __launch_bounds__(VT) void eval_pred_kernel(const fx_video_attn* vids
   pred[v.pred_off + t] = bc;
 }
 
+// ------------------------------------------------------------------ transcript prediction (blocks.py:264-275)
+// The tokens are the video's transcript gl[0..G): pred = gl[argmax_n((1 - w) softmax_n(attn[row(t), 0..G))[n] +
+// w softmax_c(flogit[t])[gl[n]])], first maximum.  The softmax over the attention values (probabilities
+// already) is the reference's.  One frame per thread, the transcript in LDS (ids clamped to the class range),
+// segment-level attention read through seg_id: no frames x tokens table.
+__global__ __launch_bounds__(VT) void eval_pred_trans_kernel(const fx_video_attn* vids, float w, int32_t* pred) {
+  extern __shared__ int tr[];   // [G] transcript
+  const fx_video_attn& v = vids[blockIdx.y];
+  const int C = v.C1 - 1, G = v.G;
+  if ((long long)blockIdx.x * VT >= v.T) return;      // (the whole workgroup: no barrier is skipped by a part of it)
+  for (int n = threadIdx.x; n < G; n += VT) tr[n] = min(max(v.gl[n], 0), C - 1);
+  __syncthreads();
+  const int t = blockIdx.x * VT + threadIdx.x;
+  if (t >= v.T) return;
+  const int row = v.seg_id ? v.seg_id[t] : t;
+  const float* arow = v.attn + (long long)row * v.lda;
+  const float* fl = v.flogit + (long long)t * v.ldf;
+  float fm = -INFINITY;
+  for (int c = 0; c < C; ++c) fm = fmaxf(fm, fl[c]);
+  float fs = 0.f;
+  for (int c = 0; c < C; ++c) fs += expf(fl[c] - fm);
+  const float finv = 1.f / fs;
+  float am = -INFINITY;
+  for (int n = 0; n < G; ++n) am = fmaxf(am, arow[n]);
+  float as = 0.f;
+  for (int n = 0; n < G; ++n) as += expf(arow[n] - am);
+  const float ainv = 1.f / as;
+  float bv = -INFINITY;
+  int bn = 0;
+  for (int n = 0; n < G; ++n) {
+    const float p = (1.f - w) * (expf(arow[n] - am) * ainv) + w * (expf(fl[tr[n]] - fm) * finv);
+    if (p > bv) {
+      bv = p;
+      bn = n;
+    }
+  }
+  pred[v.pred_off + t] = tr[bn];
+}
+
 }  // namespace
 }  // namespace fx
 
@@ -722,6 +762,29 @@ int fx_eval_pred(const fx_video_attn* vids_host, const fx_video_attn* vids_dev, 
   FX_REQUIRE((size_t)QC * sizeof(float) <= 60 * 1024, "eval_pred: too many token x class probabilities");
   fx_launch(eval_pred_kernel, dim3(cdiv(T, VT), nvid), dim3(VT), sizeof(float) * QC, (hipStream_t)stream,
                      vids_dev, mwt, pred);
+  FX_CHECK_HIP(hipGetLastError());
+  return FX_OK;
+}
+
+int fx_eval_pred_trans(const fx_video_attn* vids_host, const fx_video_attn* vids_dev, int nvid, float mwt,
+                       int32_t* pred, void* stream) {
+  FX_REQUIRE(vids_host && vids_dev && nvid > 0 && pred, "eval_pred_trans: bad arguments");
+  int T = 0, G = 0;
+  for (int i = 0; i < nvid; ++i) {
+    const fx_video_attn& v = vids_host[i];
+    FX_REQUIRE(v.G >= 1, "eval_pred_trans: empty transcript");
+    FX_REQUIRE(v.G <= v.Q, "eval_pred_trans: transcript longer than the token rows (G > Q)");
+    FX_REQUIRE(v.gl, "eval_pred_trans: video without a transcript");
+    FX_REQUIRE(v.flogit && v.C1 >= 2, "eval_pred_trans: video without logits");
+    FX_REQUIRE(v.attn && v.T >= 0 && v.lda >= v.G && v.ldf >= v.C1 - 1 && v.pred_off >= 0,
+               "eval_pred_trans: bad sizes");
+    T = std::max(T, v.T);
+    G = std::max(G, v.G);
+  }
+  FX_REQUIRE((size_t)G * sizeof(int) <= 60 * 1024, "eval_pred_trans: transcript too long");
+  if (T == 0) return FX_OK;
+  fx_launch(eval_pred_trans_kernel, dim3(cdiv(T, VT), nvid), dim3(VT), sizeof(int) * G, (hipStream_t)stream,
+            vids_dev, mwt, pred);
   FX_CHECK_HIP(hipGetLastError());
   return FX_OK;
 }

@@ -15,6 +15,7 @@ autograd as usual.
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from . import native as nx
@@ -461,6 +462,76 @@ def process_feature(x, n, class_sep=None):
     if class_sep >= n:
         raise ValueError(f"process_feature: class_sep {class_sep} leaves no second group of {n} class channels")
     return ProcessFeature2Fn.apply(_2d(x), int(class_sep), int(n - class_sep))
+
+
+# ---------------------------------------------------------------------------
+# Token embedding of a transcript input (blocks.py:75-79)
+# ---------------------------------------------------------------------------
+
+def token_csr(ids, nclass):
+    """Class -> rows grouping of the token ids as a CSR pair (coff (nclass + 1), clist (R)), int32: rows
+    clist[coff[c]:coff[c + 1]] are those with ids == c, in increasing order (fx_token_embed_bwd sums them in
+    that order).  Raises on an id outside [0, nclass)."""
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    if ids.size and (ids.min() < 0 or ids.max() >= nclass):
+        raise ValueError(f"token_csr: class id outside [0, {nclass}): {int(ids.min())}..{int(ids.max())}")
+    coff = np.zeros(nclass + 1, dtype=np.int32)
+    np.cumsum(np.bincount(ids, minlength=nclass), out=coff[1:])
+    return coff, np.argsort(ids, kind="stable").astype(np.int32)
+
+
+class TokenEmbedFn(torch.autograd.Function):
+    """``action_embed(transcript) + action_pe`` for the stacked token rows of every video of a pass:
+    out[r] = W[ids[r]] + pe[pos[r]] (``pe`` None: no positional rows).  ``ids`` / ``pos`` are host int32
+    arrays (the transcript is built on the host); one upload carries them and the backward's class -> rows
+    lists.  The weight gradient is a gather in row order (no atomics): accumulated into ``W.grad`` when W is
+    a leaf (grad_target), written whole otherwise."""
+
+    @staticmethod
+    def forward(ctx, W, pe, ids, pos):
+        lib = nx.load()
+        C, A = W.shape
+        R = int(ids.shape[0])
+        dev = W.device
+        coff, clist = token_csr(ids, C) if R else (np.zeros(C + 1, np.int32), np.zeros(0, np.int32))
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        pos = None if (pe is None or pos is None) else np.ascontiguousarray(pos, dtype=np.int32)
+        if pe is not None and pos is None:
+            raise ValueError("token_embed: a positional table needs the rows' positions")
+        host = np.concatenate([ids, pos if pos is not None else ids[:0], coff, clist])
+        tab = torch.from_numpy(host).to(dev, non_blocking=True)
+        p0 = tab.data_ptr()
+        npos = R if pos is not None else 0
+        out = _empty(R, A, device=dev)
+        _check(lib.fx_token_embed_fwd(nx.ptr(W), nx.ld(W), C, A, ids.ctypes.data, None if pos is None else
+                                      pos.ctypes.data, p0, None if pos is None else p0 + 4 * R, R, nx.ptr(pe),
+                                      nx.ld(pe), 0 if pe is None else pe.shape[0], nx.ptr(out), A, nx.stream()),
+               "fx_token_embed_fwd")
+        ctx.csr = (coff, clist, tab, p0 + 4 * (R + npos), p0 + 4 * (R + npos + C + 1))
+        ctx.dims = (R, C, A)
+        ctx.save_for_backward(W)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = nx.load()
+        (W,) = ctx.saved_tensors
+        R, C, A = ctx.dims
+        if not ctx.needs_input_grad[0] or R == 0:
+            return None, None, None, None
+        coff, clist, _tab, coff_d, clist_d = ctx.csr
+        dout = dout.contiguous()
+        acc = int(W.is_leaf)
+        dwb, dw_ret = (grad_target(W) if acc else (_empty(C, A, device=W.device),) * 2)
+        _check(lib.fx_token_embed_bwd(nx.ptr(dout), nx.ld(dout), R, C, A, coff.ctypes.data, clist.ctypes.data, coff_d,
+                                      clist_d, nx.ptr(dwb), nx.ld(dwb), acc, nx.stream()), "fx_token_embed_bwd")
+        return dw_ret, None, None, None
+
+
+def token_embed(W, ids, pe=None, pos=None):
+    """Embedded token rows (R, A) of the host id list ``ids``; ``pe`` (npe, A) + host ``pos`` add positional rows."""
+    pe2 = None if pe is None else _2d(pe)
+    return TokenEmbedFn.apply(W, pe2, np.asarray(ids), None if pos is None else np.asarray(pos))
 
 
 # ---------------------------------------------------------------------------

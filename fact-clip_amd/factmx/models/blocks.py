@@ -15,6 +15,7 @@ per-video split views ``_vrec`` and the stacked ``_bt`` of every ``forward_batch
 ``dp_marks`` (block inputs marked for factmx.dp: this file's models only) and ``match_before_merge`` (where
 the last block starts the loss phase's matching, see ``_TDU.forward_batch``).
 """
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -287,8 +288,16 @@ class InputBlock(Block):
         f = _frame_branch_batch(self.frame_branch, f2, vb)
         self._dp_mark(f)
         f_out, f_cl = fxf.process_feature(f, self.nclass)
-        a = fxf.decoder(self.action_branch, a2, f_out, pos=fpos, query_pos=apos, nvid=vb.nvid,
-                        mem_off=vb.f_off if vb.ragged else None)
+        br = self.action_branch
+        if isinstance(br, basic.ActionUpdate_GRU):
+            # Bi.a in gru / gru_om (transcript tokens only): every video's tokens as one sequence of the BiGRU
+            a = fxf.gru(br.gru, a2, seq_off=vb.a_off)
+            a = fxf.layer_norm(a, br.layernorm.weight, br.layernorm.bias, br.layernorm.eps)
+            if isinstance(br.out_map, nn.Linear):
+                a = fxf.linear(a, br.out_map.weight, br.out_map.bias)
+        else:
+            a = fxf.decoder(br, a2, f_out, pos=fpos, query_pos=apos, nvid=vb.nvid,
+                            mem_off=vb.f_off if vb.ragged else None)
         a_out, a_cl = fxf.process_feature(a, self.nclass + 1)
         _save_views(self, vb, f_cl, a_cl, (a_out, self.nclass + 1))
         return f_out, a_out
@@ -600,13 +609,19 @@ class _FACTBase(nn.Module):
         """A model-level head on the last block's stacked frame rows: None, or its restore(v)."""
         return None
 
-    def _forward_batch(self, seq_list, on_a2f=None):
+    def _forward_batch(self, seq_list, on_a2f=None, transcripts=None):
         """All videos through the blocks in lockstep (see _forward_videos); returns restore(v), which
         points every side-channel attribute at video v's views.  ``on_a2f`` (vloss.EarlyMatch,
         vn_vloss.BatchMatch) runs when the last block's token logits and token -> frame (segment)
-        attention exist."""
+        attention exist.  ``transcripts`` (FACT.trans): per video its host class list, all of one length N;
+        the tokens are then their embedded entries (fxf.token_embed with the action_pe rows, blocks.py:75-79),
+        N per video, and carry no position (the reference passes zeros)."""
         nvid = len(seq_list)
-        Q = self.cfg.FACT.ntoken
+        if transcripts is not None:
+            Q = len(transcripts[0])
+            assert Q >= 1 and all(len(t) == Q for t in transcripts), "one pass takes transcripts of one length"
+        else:
+            Q = self.cfg.FACT.ntoken
         vb = _VideoBatch(nvid, [int(s.shape[0]) for s in seq_list], Q)
         vb.on_a2f, vb.last, vb.match_before_merge = on_a2f, self.block_list[-1], self.match_before_merge
         if on_a2f is not None:
@@ -623,9 +638,21 @@ class _FACTBase(nn.Module):
         f2 = torch.cat(frames, 0)
         fpe = [_frame_pos(self.frame_pe, s.unsqueeze(1)) for s in seq_list]
         fpos = None if fpe[0] is None else torch.cat([p.squeeze(1) for p in fpe], 0)
-        # one shared gradient buffer for the query table's readers (fxf.PosGradSink: no pairwise adds)
-        apos = fxf.pos_sink(self.action_query.squeeze(1).repeat(nvid, 1))
-        a2 = torch.zeros_like(apos)
+        if transcripts is not None:
+            vb.transcripts = [np.asarray(t, dtype=np.int32) for t in transcripts]
+            if Q > self.action_pe.pe.shape[0]:
+                self.action_pe(torch.empty(Q, 0))          # (grows the table, as PositionalEncoding.forward)
+            a2 = fxf.token_embed(self.action_embed.weight, np.concatenate(vb.transcripts), self.action_pe.pe,
+                                 np.tile(np.arange(Q, dtype=np.int32), nvid))
+            # The reference passes zero query positions for a transcript input (blocks.py:79).  None would
+            # save the adds, and fx_decoder_* / fx_x2y_* have a branch for a NULL position, but no test of the
+            # suite runs the decoders' branch (every fixture and layer test gives positions), so a zero tensor
+            # without gradient keeps the transcript model on the kernel path that is covered: x + 0 == x bitwise.
+            apos = torch.zeros_like(a2)
+        else:
+            # one shared gradient buffer for the query table's readers (fxf.PosGradSink: no pairwise adds)
+            apos = fxf.pos_sink(self.action_query.squeeze(1).repeat(nvid, 1))
+            a2 = torch.zeros_like(apos)
         for k, blk in enumerate(self.block_list):
             self._mark(k, blk, f2)
             f2, a2 = blk.forward_batch(f2, a2, fpos, apos, vb)
@@ -795,6 +822,7 @@ class _VideoBatch:
         # the loss phase's hooks (set by the model): on_a2f(vb, token logits, a2f attention[, segments]) runs in
         # block ``last``, before sf_merge or after the frame branch is issued (_TDU.forward_batch)
         self.on_a2f = self.last = self.while_waiting = None
+        self.transcripts = None     # FACT.trans: per video its transcript (host int32), Q entries each
         self.match_before_merge = False
 
     def fr(self, v):
@@ -816,21 +844,40 @@ class _VideoBatch:
 # lockstep batches take the loss phase through models/vloss.py (False: per-video MatchCriterion ops)
 FUSED_LOSS = True
 
+# transcript-conditioned models (FACT.trans) take the lockstep pass and the fused loss phase (False: every
+# video alone through _run_blocks and the per-video MatchCriterion ops; A/B runs)
+TRANS_BATCH = True
+
 
 MAX_LOCKSTEP_VIDEOS = 16   # ragged frame-branch convs carry at most 16 video offsets per launch
 
 
 def _batchable(net, seq_list):
-    """The lockstep path (any video lengths, one video included) needs the fused decoders, GPU inputs
-    and no transcript input."""
-    if not seq_list or len(seq_list) > MAX_LOCKSTEP_VIDEOS or net.cfg.FACT.trans:
+    """The lockstep path (any video lengths, one video included) needs the fused decoders (or, in the input
+    block of a transcript model, the GRU branch) and GPU inputs; a transcript input needs TRANS_BATCH."""
+    if not seq_list or len(seq_list) > MAX_LOCKSTEP_VIDEOS or (net.cfg.FACT.trans and not TRANS_BATCH):
         return False
     if any(not s.is_cuda or s.shape[0] < 1 for s in seq_list):
         return False
     for blk in net.block_list:
-        if not basic._fused_decoder_ok(blk.action_branch) or not hasattr(blk, "forward_batch"):
+        if not hasattr(blk, "forward_batch"):
+            return False
+        if isinstance(blk.action_branch, basic.ActionUpdate_GRU):
+            if not (net.cfg.FACT.trans and isinstance(blk, InputBlock)):
+                return False
+        elif not basic._fused_decoder_ok(blk.action_branch):
             return False
     return True
+
+
+def transcript_passes(transcripts):
+    """How the videos of a transcript batch share lockstep passes: the decoders split the stacked token rows
+    evenly, so a batch whose transcripts all have one length (a batch of one included) is ONE pass; any
+    other batch runs every video as its own pass of one video.  Returns the passes as lists of video indices."""
+    n = len(transcripts)
+    if len({len(t) for t in transcripts}) <= 1:
+        return [list(range(n))] if n else []
+    return [[v] for v in range(n)]
 
 
 def _label_to_host(label):
@@ -875,7 +922,14 @@ def _forward_videos(net, seq_list, label_list, compute_loss):
             pending.append((save, keys, vals))
 
     net.video_segments = []     # per video: the TDU segment count of every U block (host ints, no sync)
-    if _batchable(net, seq_list):
+    batch = _batchable(net, seq_list)
+    if batch and net.cfg.FACT.trans:
+        # transcript tokens take the lockstep pass only together with the fused loss phase; everything else
+        # (no criterion yet, FUSED_LOSS off, a model vloss does not cover) runs per video, as it always did
+        if FUSED_LOSS and vloss.supported(net):
+            return _forward_transcript_videos(net, seq_list, label_list, hosts, compute_loss)
+        batch = False
+    if batch:
         fused = FUSED_LOSS and vloss.supported(net)
         early = vloss.EarlyMatch(net, hosts) if (fused and compute_loss) else None
         restore = net._forward_batch(seq_list, early)
@@ -918,3 +972,72 @@ def _forward_videos(net, seq_list, label_list, compute_loss):
             i += len(keys)
         return sum(losses) / len(losses), save_list
     return save_list
+
+
+def _finish_video_now(net, label, host, transcript, compute_loss):
+    """The per-video prediction and loss (MatchCriterion's methods) on the side channels as they stand, read
+    back at once: (save dict, loss or None).  The rare way out of a transcript pass whose term table would not
+    fit (_forward_transcript_videos)."""
+    clip = isinstance(net, FACT_CLIP)
+    dev = net.block_list[-1].frame_clogit.device
+    trans = torch.from_numpy(np.asarray(transcript, dtype=np.int64)).to(dev)
+    pred = net.eval_with_clip(trans) if clip else net.block_list[-1].eval(trans)
+    save = {"pred": pred.reshape(-1).to(torch.int64).cpu().numpy()}
+    lo = None
+    if compute_loss:
+        lo = net._loss_one_video(label, label_host=host)
+        vals = {"loss": float(lo.detach())}
+        if clip and hasattr(net, "fact_loss"):
+            vals["fact_loss"] = float(net.fact_loss.detach())
+        if clip and hasattr(net, "contrastive_loss"):
+            vals["contrastive_loss"] = float(net.contrastive_loss.detach())
+        save["loss"] = vals
+    fxf.status_raise(int(fxf.device_status(dev)[0].item()), dev)     # kernel-side failures (GRU timeout)
+    return save, lo
+
+
+def _forward_transcript_videos(net, seq_list, label_list, hosts, compute_loss):
+    """_forward_videos for a transcript-conditioned model on the lockstep path.  The transcripts come from
+    the host copies of the labels (the one wait before the forward: the token count depends on them); the
+    videos run in the passes of ``transcript_passes``, each pass with its own fused loss phase (one term
+    table, one fx_loss_terms pair, one read-back).  The batch loss is the mean over the videos, save_list
+    keeps the videos' order and the side channels hold the last video's values."""
+    transcripts = []
+    for lh, ev in hosts:
+        if ev is not None:
+            ev.synchronize()
+        transcripts.append(vloss.gt_segments(lh.numpy() if torch.is_tensor(lh) else np.asarray(lh))[2])
+    nvid = len(seq_list)
+    passes = transcript_passes(transcripts)
+    saves, segs, losses = [None] * nvid, [None] * nvid, []
+    for k, vids in enumerate(passes):
+        if k:       # the previous pass's read-back leaves the pinned buffers the next pass reuses (vloss._pinned)
+            vloss.resolve_pending()
+        seqs = [seq_list[v] for v in vids]
+        early = vloss.EarlyMatch(net, [hosts[v] for v in vids], Q=len(transcripts[vids[0]])) if compute_loss else None
+        restore = net._forward_batch(seqs, early, [transcripts[v] for v in vids])
+        restore(len(vids) - 1)
+        for i, v in enumerate(vids):
+            segs[v] = [blk._bt["S"][i] for blk in net.block_list if "S" in blk._bt]
+        try:
+            out = vloss.run(net, net._vb, compute_loss, early)
+        except vloss.TableTooLarge:
+            # more matched columns than the fused term table holds (a transcript past FX_LOSS_MAXK entries):
+            # this pass's losses and predictions run per video on the lockstep outputs, as _forward_videos does
+            for i, v in enumerate(vids):
+                restore(i)
+                saves[v], lo = _finish_video_now(net, label_list[v], hosts[v], transcripts[v], compute_loss)
+                if compute_loss:
+                    losses.append((lo, 1))
+            continue
+        if compute_loss:
+            losses.append((out[0], len(vids)))
+            out = out[1]
+        for i, v in enumerate(vids):
+            saves[v] = out[i]
+    net.video_segments = segs
+    if not compute_loss:
+        return saves
+    if len(losses) == 1:
+        return losses[0][0], saves
+    return _sum_terms([lo * (n / nvid) for lo, n in losses]), saves

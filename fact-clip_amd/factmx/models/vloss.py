@@ -63,15 +63,16 @@ def segment_weights(mc, transcript):
 
 
 def supported(net):
-    """The fused phase covers FACT / FACT_CLIP without transcripts whose last block has token->frame
-    attention (every reference config: the matching reads it).  A batch in which some video's matching
+    """The fused phase covers FACT / FACT_CLIP, with learned queries or transcript tokens (FACT.trans: a
+    video's tokens are its transcript, vb.Q of them), whose last block has token->frame attention (every
+    reference config: the matching reads it).  A batch in which some video's matching
     pairs more than FX_LOSS_MAXK columns makes run() raise TableTooLarge once the matching is known:
     the per-frame predictions (fx_eval_pred) are already enqueued by then (they only read the network's
     outputs and are recomputed by the fallback), but none of the loss launches is; the caller computes
     that batch's losses per video (loss.py's methods)."""
     from .blocks import UpdateBlock, UpdateBlockTDU
     mc = getattr(net, "mcriterion", None)
-    if mc is None or net.cfg.FACT.trans or net.cfg.Loss.match not in ("o2o", "o2m", "seq"):
+    if mc is None or net.cfg.Loss.match not in ("o2o", "o2m", "seq"):
         return False
     return isinstance(net.block_list[-1], (UpdateBlock, UpdateBlockTDU))
 
@@ -204,14 +205,13 @@ def resolve_pending():
     fxf.resolve_backward_status()
 
 
-def _stage2_labels(net, labs, G):
+def _stage2_labels(net, labs, G, Q):
     """Stage 2's tables that depend on the labels only (EarlyMatch.prepare): the holdout remap and the
     per-video InfoNCE targets (blocks.py:677-747), and the term table's host arrays -- token targets and
     matched-column slots (capacity G[v] >= K), filled after the matching -- in the pack sent with it."""
     from .blocks import FACT_CLIP
     cfg = net.cfg
     nvid = len(labs)
-    Q = cfg.FACT.ntoken
     C1 = net.num_classes + 1
     text = getattr(net, "text_embeddings", None) if isinstance(net, FACT_CLIP) else None
     use_clip = text is not None
@@ -279,8 +279,10 @@ class EarlyMatch:
     labels, one upload, ONE fx_match_cost launch for every video and an asynchronous read-back of
     the costs, so the host's Hungarian overlaps the rest of the forward on the device."""
 
-    def __init__(self, net, hosts):
+    def __init__(self, net, hosts, Q=None):
         self.net, self.hosts = net, hosts
+        # tokens per video: the learned queries, or (FACT.trans) the transcript length of the pass
+        self.Q = int(net.cfg.FACT.ntoken if Q is None else Q)
         self.done = False
         self.prepared = False
 
@@ -311,13 +313,14 @@ class EarlyMatch:
         pk.send()
         self.__dict__.update(labs=labs, gts=gts, G=G, Gmax=max(G), gt_off=gt_off, lab_off=lab_off, cw=cw,
                              cw_off=cw_off, pk=pk, base=base)
-        self.stage2 = _stage2_labels(net, labs, G)
+        self.stage2 = _stage2_labels(net, labs, G, self.Q)
         self.prepared = True
 
     def __call__(self, vb, a_cl, a2f_at, seg=None):
         net, cfg = self.net, self.net.cfg
         lib = nx.load()
         nvid, Q, fo = vb.nvid, vb.Q, vb.f_off
+        assert Q == self.Q, (Q, self.Q)
         C1 = net.num_classes + 1
         dev = a_cl.device
         self.prepare(dev)
@@ -400,12 +403,20 @@ def run(net, vb, compute_loss, early=None):
     proj = getattr(net, "_proj", None) if clip else None
     use_clip = text is not None and proj is not None
     flog = fxf.matmul_nt(proj.detach(), text, alpha=1.0 / cfg.CLIP.temp) if use_clip else last["f_cl"]
+    # FACT.trans: the prediction picks transcript entries (Block._eval_w_transcript), except with the CLIP
+    # head's text similarities, where the reference's eval_with_clip ignores the transcript
+    trans_pred = bool(cfg.FACT.trans) and not use_clip
+    eval_name = "fx_eval_pred_trans" if trans_pred else "fx_eval_pred"
+    eval_fn = getattr(lib, eval_name)
 
-    def eval_structs(pk):
+    def eval_structs(pk, gl=None):
+        """``gl``: per video the device address of its transcript (the transcript prediction reads it)."""
         off, va = pk.structs(nx.VideoAttn, nvid)
         for v in range(nvid):
             a = va[v]
             a.Q, a.C1, a.T = Q, C1, Ts[v]
+            if gl is not None:
+                a.G, a.gl = Q, gl[v]
             a.clogit, a.ldc = _ptr_rows(last["a_cl"], v * Q, C1), C1
             if "S" in last:
                 a.attn, a.lda = last["a2f_at"].data_ptr() + 4 * Q * last["s_off"][v], Q
@@ -421,10 +432,14 @@ def run(net, vb, compute_loss, early=None):
     if not compute_loss:
         pk = _Pack()
         va_off, va = eval_structs(pk)
+        tr_off = [pk.array(t, np.int32) for t in vb.transcripts] if trans_pred else None
         base = pk.alloc(dev)
+        if trans_pred:
+            for v in range(nvid):
+                va[v].G, va[v].gl = Q, base + tr_off[v]
         pk.send()
-        nx.check(lib.fx_eval_pred(ctypes.addressof(va), base + va_off, nvid, float(cfg.FACT.mwt), nx.ptr(pred),
-                                  nx.stream()), "fx_eval_pred")
+        nx.check(eval_fn(ctypes.addressof(va), base + va_off, nvid, float(cfg.FACT.mwt), nx.ptr(pred), nx.stream()),
+                 eval_name)
         host = torch.cat([pred, fxf.device_status(dev)[:1]]).cpu().numpy()
         fxf.status_raise(int(host[-1]), dev)
         return [{"pred": host[fo[v]:fo[v + 1]].astype(np.int64)} for v in range(nvid)]
@@ -453,11 +468,14 @@ def run(net, vb, compute_loss, early=None):
     _stamp("con")
     # the predictions (no matching needed): own small table, launched before the wait
     pke = _Pack()
-    va_off, va = eval_structs(pke)
+    if trans_pred and any(G[v] != Q for v in range(nvid)):
+        raise RuntimeError(f"vloss: transcript lengths {G} of a pass with {Q} token rows per video")
+    # (a video's ground-truth class list in the label tables IS its transcript)
+    va_off, va = eval_structs(pke, [base + gt_off[v][2] for v in range(nvid)] if trans_pred else None)
     pke.alloc(dev)
     pke.send()
-    nx.check(lib.fx_eval_pred(ctypes.addressof(va), pke.base + va_off, nvid, float(cfg.FACT.mwt), nx.ptr(pred),
-                              nx.stream()), "fx_eval_pred")
+    nx.check(eval_fn(ctypes.addressof(va), pke.base + va_off, nvid, float(cfg.FACT.mwt), nx.ptr(pred), nx.stream()),
+             eval_name)
 
     _stamp("eval_pred")
     # every differentiated input of the term table, its gradient a view of the table's ONE flat allocation
@@ -593,7 +611,10 @@ def run(net, vb, compute_loss, early=None):
     _stamp("fill")
     tt.send()
     _stamp("send")
-    out, loss = tt.launch(keep=(early, pke, sims, flog, text_seen))
+    # (the TDU blocks' segment tables too: the terms hold their addresses, and a later pass of the same step --
+    # a transcript batch of unequal lengths -- replaces blk._bt before this backward runs; the logits are inputs)
+    out, loss = tt.launch(keep=(early, pke, sims, flog, text_seen,
+                                [blk._bt["local"] for blk in blocks if "local" in blk._bt]))
 
     _stamp("send_lossfn")
     # the reference's side channels: last video's per-block losses, fact / contrastive terms

@@ -12,7 +12,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FACTMX_LIB", os.path.join(_HERE, "_lib", "libfactmx.so"))
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 P = ctypes.c_void_p
 I = ctypes.c_int
@@ -214,6 +214,9 @@ SIGNATURES = {
     "fx_loss_terms_bwd": (I, [P, P, I, P, I, P, P, P]),
     "fx_match_cost": (I, [P, P, I, F, F, I, P, P]),
     "fx_eval_pred": (I, [P, P, I, F, P, P]),
+    "fx_eval_pred_trans": (I, [P, P, I, F, P, P]),
+    "fx_token_embed_fwd": (I, [P, L, I, I, P, P, P, P, I, P, L, I, P, L, P]),
+    "fx_token_embed_bwd": (I, [P, L, I, I, I, P, P, P, P, P, L, I, P]),
     "fx_set_stream_precision": (I, [P, I]),
     "fx_get_stream_precision": (I, [P]),
     "fx_stream_precision_explicit": (I, [P]),

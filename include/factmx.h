@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define FX_ABI_VERSION 26
+#define FX_ABI_VERSION 27
 
 enum {
   FX_OK = 0,
@@ -918,6 +918,30 @@ int fx_match_cost(const fx_video_attn* vids_host, const fx_video_attn* vids_dev,
                   float a2fc, int Gmax, float* cost, void* stream);
 int fx_eval_pred(const fx_video_attn* vids_host, const fx_video_attn* vids_dev, int nvid, float mwt,
                  int32_t* pred, void* stream);
+/* Transcript-conditioned prediction (Block.eval with a transcript, blocks.py:264-275): the tokens are the
+ * video's transcript gl[0..G), G <= Q.  pred[pred_off + t] = gl[argmax_n((1-mwt) softmax_n(attn[row(t), 0..G))[n]
+ * + mwt softmax_c(flogit[t])[gl[n]])], first maximum; attn / lda / seg_id as above (segment-level attention is
+ * read through seg_id).  Every video is checked on the host first: G >= 1, G <= Q, gl, flogit, C1 >= 2. */
+int fx_eval_pred_trans(const fx_video_attn* vids_host, const fx_video_attn* vids_dev, int nvid, float mwt,
+                       int32_t* pred, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Token embedding of a transcript input (blocks.py:75-79), R stacked token rows.
+ * fx_token_embed_fwd: out[r, :] = W[ids[r], :] + pe[pos[r], :] (W (C, A) ldw; pe (npe, A) ldpe or NULL,
+ *   then pos may be NULL too).  ids / pos are passed twice: the host copies are range-checked before the
+ *   launch (a bad id is an error, nothing is enqueued), the kernel clamps as well.
+ * fx_token_embed_bwd: dW[c, :] (+)= sum of dout[r, :] over the rows with ids[r] == c in increasing r, the
+ *   grouping given as a CSR pair built on the host: rows clist[coff[c] .. coff[c+1]) belong to class c
+ *   (coff (C + 1), coff[C] == R, each class's rows increasing).  No float atomics: bitwise repeatable.
+ *   accumulate != 0 adds to dW (classes without rows are left alone); 0 writes every row of dW (zeros for
+ *   classes that do not occur).
+ * ---------------------------------------------------------------------- */
+int fx_token_embed_fwd(const float* W, long long ldw, int C, int A, const int32_t* ids_host,
+                       const int32_t* pos_host, const int32_t* ids_dev, const int32_t* pos_dev, int R,
+                       const float* pe, long long ldpe, int npe, float* out, long long ldo, void* stream);
+int fx_token_embed_bwd(const float* dout, long long ldd, int R, int C, int A, const int32_t* coff_host,
+                       const int32_t* clist_host, const int32_t* coff_dev, const int32_t* clist_dev, float* dW,
+                       long long lddw, int accumulate, void* stream);
 
 /* ------------------------------------------------------------------------
  * GEMM arithmetic precision, per caller stream (the stream every entry point
