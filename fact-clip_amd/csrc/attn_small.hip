@@ -33,12 +33,20 @@ __device__ __forceinline__ float wmax(float v) {
   return v;
 }
 
-// keep-scale of probability (head h, query i, key j) of video vid: 1/(1-p) or 0 -- the attention-over-T
-// kernels' mask (attn_t.hip drop_keep) with global query row vid*Lq+i and key row vid*Lk+j
-__device__ __forceinline__ float keep_scale(unsigned long long seed, unsigned thr, float p, int vid, int nvid, int nh,
-                                            int h, int Lq, int Lk, int i, int j) {
-  const unsigned long long qg = (unsigned long long)vid * Lq + i, kg = (unsigned long long)vid * Lk + j;
-  const unsigned long long idx = (qg * nh + h) * ((unsigned long long)nvid * Lk) + kg;
+constexpr int MAXV = 32;      // videos per launch (the per-video row offsets live in the kernel arguments)
+
+// rows of video v: q / o rows [qo[v], qo[v+1]), k / v rows [ko[v], ko[v+1]) (the host fills v*Lq, v*Lk for
+// an even split); Lq, Lk are the longest video's counts (the saved probabilities' per-video block)
+struct SmallOff {
+  int qo[MAXV + 1];
+  int ko[MAXV + 1];
+};
+
+// keep-scale of probability (head h, global query row qg, global key row kg of ktot): 1/(1-p) or 0 -- the
+// attention-over-T kernels' mask (attn_t.hip drop_keep)
+__device__ __forceinline__ float keep_scale(unsigned long long seed, unsigned thr, float p, int nh, int h,
+                                            unsigned long long qg, unsigned long long kg, unsigned long long ktot) {
+  const unsigned long long idx = (qg * nh + h) * ktot + kg;
   return fx_drop_bits(seed, idx) >= thr ? 1.f / (1.f - p) : 0.f;
 }
 
@@ -53,14 +61,17 @@ __global__ __launch_bounds__(NT) void mha_small_fwd_kernel(const float* q, long 
                                                            long long ldk, const float* v, long long ldv, int Lq,
                                                            int Lk, int hd, float scale, float* probs, float* o,
                                                            long long ldo, float drop_p, unsigned thr,
-                                                           unsigned long long seed) {
+                                                           unsigned long long seed, SmallOff off) {
   __shared__ float Qs[SM][SP], Ks[SM][SP], Vs[SM][SP], Ps[SM][SP];
-  const int h = blockIdx.x, vid = blockIdx.y;   // head, video (rows vid*Lq.. of q/o, vid*Lk.. of k/v)
-  q += (long long)vid * Lq * ldq;
-  k += (long long)vid * Lk * ldk;
-  v += (long long)vid * Lk * ldv;
-  o += (long long)vid * Lq * ldo;
-  probs += (long long)vid * gridDim.x * Lq * Lk;
+  const int h = blockIdx.x, vid = blockIdx.y;   // head, video (rows qo[vid].. of q/o, ko[vid].. of k/v)
+  const int q0 = off.qo[vid], k0 = off.ko[vid], ktot = off.ko[gridDim.y];
+  probs += (long long)vid * gridDim.x * Lq * Lk;   // per-video block sized by the longest video, dense inside
+  Lq = off.qo[vid + 1] - q0;
+  Lk = off.ko[vid + 1] - k0;
+  q += (long long)q0 * ldq;
+  k += (long long)k0 * ldk;
+  v += (long long)k0 * ldv;
+  o += (long long)q0 * ldo;
   load_tile(Qs, q + h * hd, ldq, Lq, hd);
   load_tile(Ks, k + h * hd, ldk, Lk, hd);
   load_tile(Vs, v + h * hd, ldv, Lk, hd);
@@ -81,7 +92,7 @@ __global__ __launch_bounds__(NT) void mha_small_fwd_kernel(const float* q, long 
     const float p = ex / wsum(ex);
     if (lane < Lk) {
       probs[((long long)h * Lq + i) * Lk + lane] = p;   // saved before dropout (backward recomputes the mask)
-      Ps[i][lane] = drop_p > 0.f ? p * keep_scale(seed, thr, drop_p, vid, gridDim.y, gridDim.x, h, Lq, Lk, i, lane) : p;
+      Ps[i][lane] = drop_p > 0.f ? p * keep_scale(seed, thr, drop_p, gridDim.x, h, q0 + i, k0 + lane, ktot) : p;
     }
   }
   __syncthreads();
@@ -99,18 +110,21 @@ __global__ __launch_bounds__(NT) void mha_small_bwd_kernel(const float* q, long 
                                                            int Lq, int Lk, int hd, float scale, float* dq,
                                                            long long lddq, float* dk, long long lddk, float* dv,
                                                            long long lddv, float drop_p, unsigned thr,
-                                                           unsigned long long seed) {
+                                                           unsigned long long seed, SmallOff off) {
   __shared__ float Qs[SM][SP], Ks[SM][SP], Vs[SM][SP], Ps[SM][SP], Ds[SM][SP], Gs[SM][SP];
   __shared__ float Ms[SM][SP];   // dropout keep-scales (training only)
   const int h = blockIdx.x, vid = blockIdx.y;
-  q += (long long)vid * Lq * ldq;
-  k += (long long)vid * Lk * ldk;
-  v += (long long)vid * Lk * ldv;
+  const int q0 = off.qo[vid], k0 = off.ko[vid], ktot = off.ko[gridDim.y];
   probs += (long long)vid * gridDim.x * Lq * Lk;
-  dout += (long long)vid * Lq * lddo;
-  if (dq) dq += (long long)vid * Lq * lddq;
-  if (dk) dk += (long long)vid * Lk * lddk;
-  if (dv) dv += (long long)vid * Lk * lddv;
+  Lq = off.qo[vid + 1] - q0;
+  Lk = off.ko[vid + 1] - k0;
+  q += (long long)q0 * ldq;
+  k += (long long)k0 * ldk;
+  v += (long long)k0 * ldv;
+  dout += (long long)q0 * lddo;
+  if (dq) dq += (long long)q0 * lddq;
+  if (dk) dk += (long long)k0 * lddk;
+  if (dv) dv += (long long)k0 * lddv;
   load_tile(Qs, q + h * hd, ldq, Lq, hd);
   load_tile(Ks, k + h * hd, ldk, Lk, hd);
   load_tile(Vs, v + h * hd, ldv, Lk, hd);
@@ -120,7 +134,7 @@ __global__ __launch_bounds__(NT) void mha_small_bwd_kernel(const float* q, long 
   if (drop)
     for (int e = threadIdx.x; e < Lq * Lk; e += NT) {
       const int i = e / Lk, j = e - i * Lk;
-      Ms[i][j] = keep_scale(seed, thr, drop_p, vid, gridDim.y, gridDim.x, h, Lq, Lk, i, j);
+      Ms[i][j] = keep_scale(seed, thr, drop_p, gridDim.x, h, q0 + i, k0 + j, ktot);
     }
   __syncthreads();
   // dP = dO V^T  -> Gs
@@ -167,18 +181,36 @@ __global__ __launch_bounds__(NT) void mha_small_bwd_kernel(const float* q, long 
     }
 }
 
+// the offsets table: `off` (host, nvid + 1, self-attention: q and k/v rows alike, Lq = Lk the longest
+// video) or the even split
+int small_off(SmallOff& t, const int* off, int nvid, int Lq, int Lk) {
+  FX_REQUIRE(nvid >= 1 && nvid <= MAXV, "mha_small: 1..32 videos");
+  int mx = 0;
+  for (int v = 0; v <= nvid; ++v) {
+    t.qo[v] = off ? off[v] : v * Lq;
+    t.ko[v] = off ? off[v] : v * Lk;
+    if (v > 0) {
+      FX_REQUIRE(t.qo[v] > t.qo[v - 1], "mha_small: row offsets must increase");
+      mx = std::max(mx, t.qo[v] - t.qo[v - 1]);
+    }
+  }
+  FX_REQUIRE(!off || (off[0] == 0 && Lq == Lk && mx <= Lq), "mha_small: row offsets start at 0, within the longest video");
+  return FX_OK;
+}
+
 }  // namespace
 
 int launch_mha_small_fwd(const float* q, long long ldq, const float* k, long long ldk, const float* v, long long ldv,
                          int Lq, int Lk, int hd, int nhead, float scale, float* probs, float* o, long long ldo,
-                         hipStream_t s, int nvid, float drop_p, unsigned long long seed) {
+                         hipStream_t s, int nvid, float drop_p, unsigned long long seed, const int* off) {
   FX_REQUIRE(Lq > 0 && Lk > 0 && hd > 0 && Lq <= SM && Lk <= SM && hd <= SM && nhead > 0,
              "mha_small: Lq, Lk, head_dim must be in [1, 64]");
-  FX_REQUIRE(nvid >= 1, "mha_small: nvid >= 1");
+  SmallOff t{};
+  FX_TRY(small_off(t, off, nvid, Lq, Lk));
   FX_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "mha_small: dropout p in [0, 1)");
   const unsigned thr = drop_p > 0.f ? std::max(fx_drop_thresh(drop_p), 1u) : 0u;
   fx_launch(mha_small_fwd_kernel, dim3(nhead, nvid), dim3(NT), 0, s, q, ldq, k, ldk, v, ldv, Lq, Lk, hd, scale,
-                     probs, o, ldo, drop_p, thr, seed);
+                     probs, o, ldo, drop_p, thr, seed, t);
   FX_CHECK_HIP(hipGetLastError());
   return FX_OK;
 }
@@ -186,14 +218,15 @@ int launch_mha_small_fwd(const float* q, long long ldq, const float* k, long lon
 int launch_mha_small_bwd(const float* q, long long ldq, const float* k, long long ldk, const float* v, long long ldv,
                          const float* probs, const float* dout, long long lddo, int Lq, int Lk, int hd, int nhead,
                          float scale, float* dq, long long lddq, float* dk, long long lddk, float* dv, long long lddv,
-                         hipStream_t s, int nvid, float drop_p, unsigned long long seed) {
+                         hipStream_t s, int nvid, float drop_p, unsigned long long seed, const int* off) {
   FX_REQUIRE(Lq > 0 && Lk > 0 && hd > 0 && Lq <= SM && Lk <= SM && hd <= SM && nhead > 0,
              "mha_small: Lq, Lk, head_dim must be in [1, 64]");
-  FX_REQUIRE(nvid >= 1, "mha_small: nvid >= 1");
+  SmallOff t{};
+  FX_TRY(small_off(t, off, nvid, Lq, Lk));
   FX_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "mha_small: dropout p in [0, 1)");
   const unsigned thr = drop_p > 0.f ? std::max(fx_drop_thresh(drop_p), 1u) : 0u;
   fx_launch(mha_small_bwd_kernel, dim3(nhead, nvid), dim3(NT), 0, s, q, ldq, k, ldk, v, ldv, probs, dout, lddo,
-                     Lq, Lk, hd, scale, dq, lddq, dk, lddk, dv, lddv, drop_p, thr, seed);
+                     Lq, Lk, hd, scale, dq, lddq, dk, lddk, dv, lddv, drop_p, thr, seed, t);
   FX_CHECK_HIP(hipGetLastError());
   return FX_OK;
 }

@@ -130,8 +130,8 @@ struct TAttnArgs {
   float* dv; long long lddv;            // bwd
   float* lse;                           // (nvid, h, qs): fwd writes, bwd reads
   float* ws;                            // partials
-  int Qv, hd, nh, Qp, Hp, Tc, nsplit;   // Qv: queries of this block; nsplit: max chunks over the videos
-  int qs, q0;                           // query rows per video (q / o / lse stride), first query of the block
+  int Qv, hd, nh, Qp, Hp, Tc, nsplit;   // Qv: queries of this block (longest video); nsplit: max chunks over the videos
+  int qs, q0;                           // longest video's query rows (lse stride), first query of the block
   int acc_kv;                           // bwd: dK / dV += (later query blocks of the same keys)
   float scale;
   int vec;                              // 16-B loads of every q / k / v / o / dout row slice
@@ -142,7 +142,13 @@ struct TAttnArgs {
   unsigned* cnt;                        // register-resident kernels: arrival counters per (video, head) for the
                                         // in-launch merge (null: partials for tattn_merge_kernel)
   int koff[MAXV + 1];                   // key / value rows of video v: [koff[v], koff[v+1])
+  int qoff[MAXV + 1];                   // query rows of video v: [qoff[v], qoff[v+1])
 };
+
+// live queries of video vid in the launch's query block [q0, q0 + Qv): 0 when the video is shorter than q0
+__device__ __forceinline__ int live_queries(const TAttnArgs& a, int vid) {
+  return max(0, min(a.Qv, a.qoff[vid + 1] - a.qoff[vid] - a.q0));
+}
 
 // keep-scale of probability (global query row qg, head h, global key row kg): 1/(1-p) or 0
 __device__ __forceinline__ float drop_keep(const TAttnArgs& a, long long qg, int h, long long kg) {
@@ -216,7 +222,9 @@ __global__ __launch_bounds__(AT) void tattn_fwd_kernel(TAttnArgs a) {
   const int Tv = a.koff[vid + 1] - a.koff[vid];
   const int t0 = c * Tc, nk = min(Tc, Tv - t0);
   if (nk <= 0) return;                  // a shorter video of a ragged batch has fewer chunks
-  const long long qrow = (long long)vid * a.qs + a.q0, krow = (long long)a.koff[vid] + t0;
+  const int Qn = live_queries(a, vid);
+  if (Qn <= 0) return;                  // a short video has no query in this block (no arrival: the merge is a launch)
+  const long long qrow = (long long)a.qoff[vid] + a.q0, krow = (long long)a.koff[vid] + t0;
   const float* qsrc = a.q + qrow * a.ldq + h * hd;
   const float* ksrc = a.k + krow * a.ldk + h * hd;
   const float* vsrc = a.v + krow * a.ldv + h * hd;
@@ -224,14 +232,14 @@ __global__ __launch_bounds__(AT) void tattn_fwd_kernel(TAttnArgs a) {
   if (a.vec) {
     Strip<NVQ> sq;
     Strip<NVK> sk, sv;
-    sq.load(Qp, Hp, qsrc, a.ldq, a.Qv, hd, tid);
+    sq.load(Qp, Hp, qsrc, a.ldq, Qn, hd, tid);
     sk.load(Tc, Hp, ksrc, a.ldk, nk, hd, tid);
     sv.load(Tc, Hp, vsrc, a.ldv, nk, hd, tid);
     sq.store(qs, lq, Qp, Hp, tid);
     sk.store(ks, lk, Tc, Hp, tid);
     sv.store(vs, lk, Tc, Hp, tid);
   } else {
-    stage_scalar(qs, lq, Qp, Hp, qsrc, a.ldq, a.Qv, hd, tid);
+    stage_scalar(qs, lq, Qp, Hp, qsrc, a.ldq, Qn, hd, tid);
     stage_scalar(ks, lk, Tc, Hp, ksrc, a.ldk, nk, hd, tid);
     stage_scalar(vs, lk, Tc, Hp, vsrc, a.ldv, nk, hd, tid);
   }
@@ -322,7 +330,7 @@ __global__ __launch_bounds__(AT) void tattn_fwd_kernel(TAttnArgs a) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int row = rt * 32 + acc_row(r, lane);
-        if (row < a.Qv && col < hd) a.out[(qrow + row) * a.ld_out + h * hd + col] = acc[r] / rowl[row];
+        if (row < Qn && col < hd) a.out[(qrow + row) * a.ld_out + h * hd + col] = acc[r] / rowl[row];
       }
     } else {
       float* po = a.ws + pid * Qp * Hp;
@@ -331,7 +339,7 @@ __global__ __launch_bounds__(AT) void tattn_fwd_kernel(TAttnArgs a) {
     }
   }
   if (a.nsplit == 1) {
-    for (int r = tid; r < a.Qv; r += AT)
+    for (int r = tid; r < Qn; r += AT)
       a.lse[((long long)vid * a.nh + h) * a.qs + a.q0 + r] = rowm[r] + __logf(rowl[r]);
     return;
   }
@@ -351,6 +359,8 @@ __global__ __launch_bounds__(AT) void tattn_fwd_kernel(TAttnArgs a) {
 __device__ void tattn_merge(const TAttnArgs& a, int h, int vid, int nvid, int stats, float mul, float* sm) {
   const int tid = threadIdx.x;
   const int Qp = a.Qp, Hp = a.Hp, hd = a.hd, nsm = a.nsplit;
+  const int Qn = live_queries(a, vid);
+  if (Qn <= 0) return;                   // (the block's workgroups of this video left no partials)
   const int ns = (a.koff[vid + 1] - a.koff[vid] + a.Tc - 1) / a.Tc;   // this video's chunks
   const long long pbase = ((long long)vid * a.nh + h) * nsm;
   const float* part = a.ws + pbase * Qp * Hp;
@@ -371,13 +381,13 @@ __device__ void tattn_merge(const TAttnArgs& a, int h, int vid, int nvid, int st
       for (int sp = 0; sp < ns; ++sp) L += __expf(w[sp * Qp + r] - M) * wl[sp * Qp + r];
       const float inv = 1.f / L;
       for (int sp = 0; sp < ns; ++sp) w[sp * Qp + r] = __expf(w[sp * Qp + r] - M) * inv;
-      if (r < a.Qv) a.lse[((long long)vid * a.nh + h) * a.qs + a.q0 + r] = M + __logf(L);
+      if (r < Qn) a.lse[((long long)vid * a.nh + h) * a.qs + a.q0 + r] = M + __logf(L);
     }
     __syncthreads();
   }
-  float* out = a.out + ((long long)vid * a.qs + a.q0) * a.ld_out + h * hd;
+  float* out = a.out + ((long long)a.qoff[vid] + a.q0) * a.ld_out + h * hd;
   const int c4 = Hp >> 2;
-  for (int e = tid; e < a.Qv * c4; e += AT) {
+  for (int e = tid; e < Qn * c4; e += AT) {
     const int r = e / c4, col = (e - r * c4) * 4;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int s0 = 0; s0 < ns; s0 += 16) {
@@ -428,19 +438,21 @@ __global__ __launch_bounds__(AT) void tattn_bwd_kernel(TAttnArgs a) {
   const int Tv = a.koff[vid + 1] - a.koff[vid];
   const int t0 = c * Tc, nk = min(Tc, Tv - t0);
   if (nk <= 0) return;
-  const long long qrow = (long long)vid * a.qs + a.q0, krow = (long long)a.koff[vid] + t0;
+  const int Qn = live_queries(a, vid);
+  if (Qn <= 0) return;                  // a short video has no query in this block (no arrival: the merge is a launch)
+  const long long qrow = (long long)a.qoff[vid] + a.q0, krow = (long long)a.koff[vid] + t0;
   const float* qsrc = a.q + qrow * a.ldq + h * hd;
   const float* dsrc = a.dout + qrow * a.lddo + h * hd;
   const float* osrc = a.o + qrow * a.ldo + h * hd;
   const float* ksrc = a.k + krow * a.ldk + h * hd;
   const float* vsrc = a.v + krow * a.ldv + h * hd;
-  if (tid < Qp) rl[tid] = tid < a.Qv ? a.lse[((long long)vid * a.nh + h) * a.qs + a.q0 + tid] : 0.f;
+  if (tid < Qp) rl[tid] = tid < Qn ? a.lse[((long long)vid * a.nh + h) * a.qs + a.q0 + tid] : 0.f;
   if (a.vec) {
     Strip<NVQ> sq, sd, so;
     Strip<NVK> sk, sv;
-    sq.load(Qp, Hp, qsrc, a.ldq, a.Qv, hd, tid);
-    sd.load(Qp, Hp, dsrc, a.lddo, a.Qv, hd, tid);
-    so.load(Qp, Hp, osrc, a.ldo, a.Qv, hd, tid);
+    sq.load(Qp, Hp, qsrc, a.ldq, Qn, hd, tid);
+    sd.load(Qp, Hp, dsrc, a.lddo, Qn, hd, tid);
+    so.load(Qp, Hp, osrc, a.ldo, Qn, hd, tid);
     sk.load(Tc, Hp, ksrc, a.ldk, nk, hd, tid);
     sv.load(Tc, Hp, vsrc, a.ldv, nk, hd, tid);
     sq.store(qs, lq, Qp, Hp, tid);
@@ -449,9 +461,9 @@ __global__ __launch_bounds__(AT) void tattn_bwd_kernel(TAttnArgs a) {
     sk.store(ks, lq, Tc, Hp, tid);
     sv.store(vs, lq, Tc, Hp, tid);
   } else {
-    stage_scalar(qs, lq, Qp, Hp, qsrc, a.ldq, a.Qv, hd, tid);
-    stage_scalar(dos, lq, Qp, Hp, dsrc, a.lddo, a.Qv, hd, tid);
-    stage_scalar(ps, lq, Qp, Hp, osrc, a.ldo, a.Qv, hd, tid);
+    stage_scalar(qs, lq, Qp, Hp, qsrc, a.ldq, Qn, hd, tid);
+    stage_scalar(dos, lq, Qp, Hp, dsrc, a.lddo, Qn, hd, tid);
+    stage_scalar(ps, lq, Qp, Hp, osrc, a.ldo, Qn, hd, tid);
     stage_scalar(ks, lq, Tc, Hp, ksrc, a.ldk, nk, hd, tid);
     stage_scalar(vs, lq, Tc, Hp, vsrc, a.ldv, nk, hd, tid);
   }
@@ -476,7 +488,7 @@ __global__ __launch_bounds__(AT) void tattn_bwd_kernel(TAttnArgs a) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int row = rt * 32 + acc_row(r, lane);
-      const float p = (col < nk && row < a.Qv) ? __expf(s[r] * a.scale - rl[row]) : 0.f;
+      const float p = (col < nk && row < Qn) ? __expf(s[r] * a.scale - rl[row]) : 0.f;
       // dropout: P_d = P keep / (1-p) multiplies V; dP = (dO V^T) keep / (1-p); D = rowsum(dO o) still
       const float kp = (a.drop_p > 0.f && p != 0.f) ? drop_keep(a, qrow + row, h, krow + col) : 1.f;
       ps[row * ls + col] = p * kp;
@@ -532,7 +544,7 @@ __global__ __launch_bounds__(AT) void tattn_bwd_kernel(TAttnArgs a) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int row = rt * 32 + acc_row(r, lane);
-        if (row < a.Qv && col < hd) a.out[(qrow + row) * a.ld_out + h * hd + col] = acc[r] * a.scale;
+        if (row < Qn && col < hd) a.out[(qrow + row) * a.ld_out + h * hd + col] = acc[r] * a.scale;
       }
     } else {
       float* po = a.ws + (((long long)vid * a.nh + h) * a.nsplit + c) * Qp * Hp;
@@ -604,6 +616,7 @@ constexpr int FOLD_MAX = 16;   // chunks per video merged inside the launch (mor
 __device__ __forceinline__ void fold_merge(const TAttnArgs& a, int vid, int h, int ns, bool stats, float mul,
                                            long long qrow, float (*wm)[32], float (*wl)[32], int* last) {
   const int tid = threadIdx.x;
+  const int Qn = live_queries(a, vid);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this thread's partial stores acknowledged
   __syncthreads();
   if (stats) TA_ST(4);
@@ -645,7 +658,7 @@ __device__ __forceinline__ void fold_merge(const TAttnArgs& a, int vid, int h, i
       for (int sp = 0; sp < ns; ++sp) L += __expf(wm[sp][tid] - M) * wl[sp][tid];
       const float inv = 1.f / L;
       for (int sp = 0; sp < ns; ++sp) wm[sp][tid] = __expf(wm[sp][tid] - M) * inv;
-      if (tid < a.Qv) a.lse[((long long)vid * a.nh + h) * a.qs + a.q0 + tid] = M + __logf(L);
+      if (tid < Qn) a.lse[((long long)vid * a.nh + h) * a.qs + a.q0 + tid] = M + __logf(L);
     }
     __syncthreads();
   }
@@ -659,7 +672,7 @@ __device__ __forceinline__ void fold_merge(const TAttnArgs& a, int vid, int h, i
       acc.z += wgt * x[sp].z;
       acc.w += wgt * x[sp].w;
     }
-  if (mq < a.Qv) {
+  if (mq < Qn) {
     float* o = a.out + (qrow + mq) * a.ld_out + h * 32 + md;
     o[0] = acc.x * mul;
     o[1] = acc.y * mul;
@@ -679,13 +692,14 @@ __global__ __launch_bounds__(AT) void tattn_fwd32_kernel(TAttnArgs a) {
   const int Tv = a.koff[vid + 1] - a.koff[vid];
   const int t0 = c * a.Tc, nk = min(a.Tc, Tv - t0);
   if (nk <= 0) return;
-  const long long qrow = (long long)vid * a.qs + a.q0, krow = (long long)a.koff[vid] + t0;
+  const int Qn = live_queries(a, vid);   // >= 1: these kernels run one query block (q0 = 0)
+  const long long qrow = (long long)a.qoff[vid] + a.q0, krow = (long long)a.koff[vid] + t0;
   const int kw0 = w * 32 * KT;
   // every load first: q and K fragments, V columns
   float4 qf[4], kf[KT][4];
   float vf[KT][16];
   {
-    const float* qp = a.q + (qrow + min(li, a.Qv - 1)) * a.ldq + h * 32 + 16 * lh;
+    const float* qp = a.q + (qrow + min(li, Qn - 1)) * a.ldq + h * 32 + 16 * lh;
 #pragma unroll
     for (int q = 0; q < 4; ++q) qf[q] = ld4g(qp + 4 * q);
     // (every K fragment before the first V column: loads complete in issue order, so S = q K^T then waits
@@ -778,7 +792,7 @@ __global__ __launch_bounds__(AT) void tattn_fwd32_kernel(TAttnArgs a) {
       L += f * xl[ww][q];
     }
     if (direct) {
-      if (q < a.Qv) {
+      if (q < Qn) {
         float* op = a.out + (qrow + q) * a.ld_out + h * 32 + d0;
         op[0] = O.x / L;
         op[1] = O.y / L;
@@ -819,9 +833,10 @@ __global__ __launch_bounds__(AT) void tattn_bwd32_kernel(TAttnArgs a) {
   const int Tv = a.koff[vid + 1] - a.koff[vid];
   const int t0 = c * a.Tc, nk = min(a.Tc, Tv - t0);
   if (nk <= 0) return;
-  const long long qrow = (long long)vid * a.qs + a.q0, krow = (long long)a.koff[vid] + t0;
+  const int Qn = live_queries(a, vid);   // >= 1: these kernels run one query block (q0 = 0)
+  const long long qrow = (long long)a.qoff[vid] + a.q0, krow = (long long)a.koff[vid] + t0;
   const int kw0 = w * 32 * KT;
-  const int Qv = a.Qv;
+  const int Qv = Qn;
   // every load first.  Query-side fragments (query li, d 16 lh ..): q, dO, o; query-side columns (query
   // acc_row(j), d li): q, dO (the B operands of dK and dV); key side: K and V fragments (key li, d 16 lh ..)
   // and K columns (key acc_row(j), d li) for dq
@@ -1044,6 +1059,15 @@ static int tattn_setup(TAttnArgs& a, int nvid, int Qv, int Tv, int hd, int nh, c
     Tmax = std::max(Tmax, k1 - k0);
   }
   ktot = a.koff[nvid];
+  int Qmax = 0;
+  for (int v = 0; v <= nvid; ++v) {
+    a.qoff[v] = opt && opt->qoff ? opt->qoff[v] : v * Qv;
+    if (v > 0) {
+      FX_REQUIRE(a.qoff[v] > a.qoff[v - 1], "attention over T: every video needs >= 1 query row, offsets increasing");
+      Qmax = std::max(Qmax, a.qoff[v] - a.qoff[v - 1]);
+    }
+  }
+  FX_REQUIRE(a.qoff[0] >= 0 && Qmax <= Qv, "attention over T: query offsets from >= 0, Qv the longest video");
   const float p = opt ? opt->drop_p : 0.f;
   FX_REQUIRE(p >= 0.f && p < 1.f, "attention over T: dropout p in [0, 1)");
   a.drop_p = p;

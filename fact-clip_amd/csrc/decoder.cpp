@@ -144,6 +144,14 @@ int dec_tmax(const fx_decoder_params* p, int T, int nvid) {
   return m;
 }
 
+// tokens of the longest video (ragged token rows: tok_off; else R / nvid each)
+int dec_qmax(const fx_decoder_params* p, int R, int nvid) {
+  if (!p->tok_off) return R / nvid;
+  int m = 0;
+  for (int v = 0; v < nvid; ++v) m = std::max(m, p->tok_off[v + 1] - p->tok_off[v]);
+  return m;
+}
+
 // the attention-core workspace: cross attention over the frames, self attention over > 64 tokens
 long long dec_attn_ws(const fx_decoder_params* p, int nvid, int Qv, int Tv) {
   const int hd = p->A / p->nhead;
@@ -155,7 +163,9 @@ long long dec_attn_ws(const fx_decoder_params* p, int nvid, int Qv, int Tv) {
 DecLayout dec_layout(const fx_decoder_params* p, int R, int T, int has_qpos, int has_mpos, int nvid) {
   DecLayout L{};
   const long long A = p->A, FF = p->FF, h = p->nhead, RA = (long long)R * A;
-  const long long Qv = R / nvid, Tv = dec_tmax(p, T, nvid);   // tokens / frames (longest video) per video
+  // tokens / frames per video, of the longest video: every per-video block (saved probabilities, lse) has
+  // the longest video's stride, a shorter video's tail is never read
+  const long long Qv = dec_qmax(p, R, nvid), Tv = dec_tmax(p, T, nvid);
   long long o = 0;
   L.xq = o; o += al64(has_qpos ? RA : 0);
   L.qkv = o; o += al64(3 * RA);
@@ -227,7 +237,13 @@ DecLayout dec_layout(const fx_decoder_params* p, int R, int T, int has_qpos, int
 
 int dec_check(const fx_decoder_params* p, int R, int T, int nvid) {
   FX_REQUIRE(p && p->num_layers >= 1 && p->num_layers <= MAXL, "decoder: 1..16 layers");
-  FX_REQUIRE(nvid >= 1 && nvid <= 32 && R % nvid == 0, "decoder: 1..32 videos, token rows split evenly");
+  FX_REQUIRE(nvid >= 1 && nvid <= 32, "decoder: 1..32 videos");
+  if (p->tok_off) {
+    FX_REQUIRE(p->tok_off[0] == 0 && p->tok_off[nvid] == R, "decoder: token offsets must span [0, R]");
+    for (int v = 0; v < nvid; ++v) FX_REQUIRE(p->tok_off[v + 1] > p->tok_off[v], "decoder: >= 1 token per video, offsets increasing");
+  } else {
+    FX_REQUIRE(R % nvid == 0, "decoder: token rows split evenly (or tok_off)");
+  }
   if (p->cross) {
     if (p->mem_off) {
       FX_REQUIRE(p->mem_off[0] == 0 && p->mem_off[nvid] == T, "decoder: memory offsets must span [0, T]");
@@ -276,7 +292,7 @@ int linear_fwd_res_drop(const float* x, long long ldx, int M, int K, const float
 bool dec_tok_ok(const fx_decoder_params* p, int R, int nvid, const void* const* ptrs, int nptr,
                 const long long* lds, int nld) {
   if (!knobs().dec_tok) return false;
-  const int Qv = R / nvid, A = p->A;
+  const int Qv = dec_qmax(p, R, nvid), A = p->A;
   bool ok = Qv >= 1 && Qv <= 32 && p->nhead * 32 == A && A <= TOK_MAXSA && p->FF % 32 == 0 && p->FF >= A &&
             p->FF <= TOK_MAXK && 3 * A <= TOK_MAXK && p->out_dim >= 4 && p->out_dim % 4 == 0 && p->out_dim <= TOK_MAXK;
   for (int i = 0; i < nptr && ok; ++i) ok = ptrs[i] == nullptr || ((uintptr_t)ptrs[i] & 15) == 0;
@@ -297,7 +313,12 @@ struct TokBuild {
   TokProgram prog{};
   hipStream_t s;
   int* status;
+  int toff[TOK_MAXV + 1] = {};   // token-row offsets of the attention items' videos (every program of the call)
   explicit TokBuild(hipStream_t st, int* stat) : s(st), status(stat) {}
+  // tok_off (host, nvid + 1) or the even split of R rows
+  void offsets(const int* tok_off, int R, int nvid) {
+    for (int v = 0; v <= nvid; ++v) toff[v] = tok_off ? tok_off[v] : v * (R / nvid);
+  }
   static int items(const TokPhase& P) {
     if (P.op == TOK_SAFWD || P.op == TOK_MHABWD) return P.nvid * P.nh;
     if (P.op == TOK_LNROWS) return (P.M + 31) / 32;
@@ -310,6 +331,7 @@ struct TokBuild {
     prog.G = std::min(G, 256);
     prog.status = reinterpret_cast<unsigned*>(status);
     prog.spin_max = tok_spin_max();
+    std::copy(toff, toff + TOK_MAXV + 1, prog.toff);
     FX_REQUIRE(status, "decoder: the persistent token kernel needs the caller's status word (fx_decoder_params.status)");
     prof_begin(8, s);
     FX_TRY(launch_tok(prog, s));
@@ -363,6 +385,7 @@ int dec_fwd_tok(const fx_decoder_params* p, const float* tgt, long long ldt, int
   const float pd = p->dropout, pa = p->attn_dropout;
   const float scale = 1.0f / std::sqrt((float)hd);
   TokBuild tb(s, p->status);
+  tb.offsets(p->tok_off, R, nvid);
   auto blk = [&](int l) { return saved + L.layers + (long long)l * L.per_layer; };
   auto lnp = [&](TokPhase* P, const float* w, const float* b) {
     P->ln.w = w;
@@ -468,6 +491,7 @@ int dec_fwd_tok(const fx_decoder_params* p, const float* tgt, long long ldt, int
       FX_TRY(tb.flush());
       TAttnOpts o;
       o.koff = p->mem_off;
+      o.qoff = p->tok_off;
       o.drop_p = pa;
       o.drop_seed = dec_seed(p, l, 2);
       FX_TRY(launch_tattn_fwd(b + L.qc, A, kv + (long long)l * A, AL2, kv + (long long)(NL + l) * A, AL2, nvid, Qv, Tv,
@@ -524,6 +548,7 @@ int dec_bwd_tok(const fx_decoder_params* p, int R, int nvid, int Qv, int Tv, con
   const float pd = p->dropout, pa = p->attn_dropout;
   const float scale = 1.0f / std::sqrt((float)hd);
   TokBuild tb(s, p->status);
+  tb.offsets(p->tok_off, R, nvid);
   auto blk = [&](int l) { return saved + L.layers + (long long)l * L.per_layer; };
   auto dy_slot = [&](int k, int l) { return ws + L.gdy + ((long long)k * NL + l) * RA; };
   auto slot_u = [&](int k, int l) { return ws + L.gdu + ((long long)k * NL + l) * RA; };
@@ -616,6 +641,7 @@ int dec_bwd_tok(const fx_decoder_params* p, int R, int nvid, int Qv, int Tv, con
       const float* kv = saved + L.kv;
       TAttnOpts o;
       o.koff = p->mem_off;
+      o.qoff = p->tok_off;
       o.drop_p = pa;
       o.drop_seed = dec_seed(p, l, 2);
       FX_TRY(launch_tattn_bwd(b + L.qc, A, kv + (long long)l * A, AL2, kv + (long long)(NL + l) * A, AL2, b + L.oca, A,
@@ -670,7 +696,7 @@ int fx_decoder_fwd(const fx_decoder_params* p, const float* tgt, long long ldt, 
                    long long ldqp, const float* mem, long long ldm, int T, int nvid, const float* mpos, long long ldmp,
                    float* out, long long ldo, float* saved, float* workspace, void* stream) {
   FX_TRY(dec_check(p, R, T, nvid));
-  const int Qv = R / nvid, Tv = dec_tmax(p, T, nvid);
+  const int Qv = dec_qmax(p, R, nvid), Tv = dec_tmax(p, T, nvid);
   hipStream_t s = (hipStream_t)stream;
   const int A = p->A, FF = p->FF, h = p->nhead, hd = A / h, NL = p->num_layers;
   const long long RA = (long long)R * A;
@@ -749,9 +775,10 @@ int fx_decoder_fwd(const fx_decoder_params* p, const float* tgt, long long ldt, 
     }
     if (Qv <= kSmallTok) {
       FX_TRY(launch_mha_small_fwd(qkv, 3 * A, qkv + A, 3 * A, qkv + 2 * A, 3 * A, Qv, Qv, hd, h, scale, b + L.psa,
-                                  b + L.osa, A, s, nvid, pa, dec_seed(p, l, 0)));
+                                  b + L.osa, A, s, nvid, pa, dec_seed(p, l, 0), p->tok_off));
     } else {   // more tokens than the LDS-resident kernel holds: the attention-over-T kernels, lse kept in psa
       TAttnOpts o;
+      o.koff = o.qoff = p->tok_off;   // (self-attention: the keys are the video's own token rows)
       o.drop_p = pa;
       o.drop_seed = dec_seed(p, l, 0);
       FX_TRY(launch_tattn_fwd(qkv, 3 * A, qkv + A, 3 * A, qkv + 2 * A, 3 * A, nvid, Qv, Qv, hd, h, scale, b + L.osa, A,
@@ -775,6 +802,7 @@ int fx_decoder_fwd(const fx_decoder_params* p, const float* tgt, long long ldt, 
       // every video's tokens over its own frames, all heads, one fused launch (attn_t.hip)
       TAttnOpts o;
       o.koff = p->mem_off;
+      o.qoff = p->tok_off;
       o.drop_p = pa;
       o.drop_seed = dec_seed(p, l, 2);
       FX_TRY(launch_tattn_fwd(b + L.qc, A, kv + (long long)l * A, AL2, kv + (long long)(NL + l) * A, AL2, nvid, Qv, Tv,
@@ -821,7 +849,7 @@ int fx_decoder_bwd(const fx_decoder_params* p, const fx_decoder_grads* g, const 
                    float* dmem, long long lddm, float* dmpos, long long lddmp, const float* saved, float* workspace,
                    void* stream) {
   FX_TRY(dec_check(p, R, T, nvid));
-  const int Qv = R / nvid, Tv = dec_tmax(p, T, nvid);
+  const int Qv = dec_qmax(p, R, nvid), Tv = dec_tmax(p, T, nvid);
   hipStream_t s = (hipStream_t)stream;
   const int A = p->A, FF = p->FF, h = p->nhead, hd = A / h, NL = p->num_layers;
   const long long RA = (long long)R * A;
@@ -895,6 +923,7 @@ int fx_decoder_bwd(const fx_decoder_params* p, const fx_decoder_grads* g, const 
       const float* kv = saved + L.kv;
       TAttnOpts o;
       o.koff = p->mem_off;
+      o.qoff = p->tok_off;
       o.drop_p = pa;
       o.drop_seed = dec_seed(p, l, 2);
       FX_TRY(launch_tattn_bwd(b + L.qc, A, kv + (long long)l * A, AL2, kv + (long long)(NL + l) * A, AL2, b + L.oca, A,
@@ -916,9 +945,10 @@ int fx_decoder_bwd(const fx_decoder_params* p, const fx_decoder_grads* g, const 
     if (Qv <= kSmallTok) {
       FX_TRY(launch_mha_small_bwd(qkv, 3 * A, qkv + A, 3 * A, qkv + 2 * A, 3 * A, b + L.psa, dO, A, Qv, Qv, hd, h,
                                   scale, dQKV, 3 * A, dQKV + A, 3 * A, dQKV + 2 * A, 3 * A, s, nvid, pa,
-                                  dec_seed(p, l, 0)));
+                                  dec_seed(p, l, 0), p->tok_off));
     } else {
       TAttnOpts o;
+      o.koff = o.qoff = p->tok_off;   // (self-attention: the keys are the video's own token rows)
       o.drop_p = pa;
       o.drop_seed = dec_seed(p, l, 0);
       FX_TRY(launch_tattn_bwd(qkv, 3 * A, qkv + A, 3 * A, qkv + 2 * A, 3 * A, b + L.osa, A, dO, A, b + L.psa, nvid, Qv,

@@ -167,15 +167,18 @@ int linear_bwd_pair(const fx_gemm_desc& dwdb, const fx_gemm_desc& dx, hipStream_
 // drop_p > 0: attention-probability dropout with attn_t.hip's mask (TAttnOpts), probs saved un-dropped
 // nvid independent problems stacked by rows (video v: q/o rows v*Lq.., k/v rows v*Lk..);
 // probs (nvid, nhead, Lq, Lk) saved; o (Lq, nhead*hd) with row stride ldo.
+// off (host, nvid + 1 row offsets from 0, self-attention): video v owns q/o and k/v rows [off[v], off[v+1]);
+// Lq = Lk is then the longest video's count, the probs block of a video stays Lq * Lk per head (dense inside)
 int launch_mha_small_fwd(const float* q, long long ldq, const float* k, long long ldk, const float* v,
                          long long ldv, int Lq, int Lk, int hd, int nhead, float scale, float* probs, float* o,
                          long long ldo, hipStream_t s, int nvid = 1, float drop_p = 0.f,
-                         unsigned long long seed = 0);
+                         unsigned long long seed = 0, const int* off = nullptr);
 // dq, dk, dv written (nullable) with their row strides
 int launch_mha_small_bwd(const float* q, long long ldq, const float* k, long long ldk, const float* v,
                          long long ldv, const float* probs, const float* dout, long long lddo, int Lq, int Lk, int hd,
                          int nhead, float scale, float* dq, long long lddq, float* dk, long long lddk, float* dv,
-                         long long lddv, hipStream_t s, int nvid = 1, float drop_p = 0.f, unsigned long long seed = 0);
+                         long long lddv, hipStream_t s, int nvid = 1, float drop_p = 0.f, unsigned long long seed = 0,
+                         const int* off = nullptr);
 
 // ---- fused multi-head attention of queries over T frames (attn_t.hip) ---------------------
 // nvid videos stacked by rows (queries v*Qv.., keys/values v*Tv.. or opt->koff); head h = columns
@@ -183,6 +186,8 @@ int launch_mha_small_bwd(const float* q, long long ldq, const float* k, long lon
 // dk, dv (rows: one per key) and writes dq.  More than 64 queries run as blocks of 64.
 struct TAttnOpts {
   const int* koff = nullptr;        // host (nvid + 1) key-row offsets of ragged videos; Tv = the longest
+  const int* qoff = nullptr;        // host (nvid + 1) query-row offsets of ragged videos; Qv = the longest
+                                    // (lse then (nvid, nhead, Qv) with the longest video's stride)
   float drop_p = 0.f;               // attention-probability dropout (training)
   unsigned long long drop_seed = 0; // mask of probability (query row qg, head h, key row kg):
                                     // fx_drop_bits(seed, (qg * nhead + h) * total_key_rows + kg)

@@ -11,6 +11,7 @@ namespace fx {
 constexpr int TOK_MAXK = 768;    // K of a GEMM phase (its 32-row A tile is staged whole in LDS)
 constexpr int TOK_MAXSA = 256;   // d_model of a self-attention item (head dim 32 x heads)
 constexpr int TOK_MAXPH = 8;     // phases per launch
+constexpr int TOK_MAXV = 32;     // videos of the attention items
 
 enum TokOp { TOK_GEMM = 0, TOK_SAFWD = 1, TOK_MHABWD = 2, TOK_LNROWS = 3 };
 // how a phase's A rows are staged: as stored; LayerNorm forward of them (the stored rows are the
@@ -61,11 +62,12 @@ struct TokPhase {
   float* c;
   long long ldc;
   TokLN ln;
-  // attention items (SAFWD / MHABWD): nvid videos of Qv tokens, nh heads of 32, K = nh * 32
+  // attention items (SAFWD / MHABWD): nvid videos of <= Qv tokens (Qv: the longest video's; video v owns
+  // rows [toff[v], toff[v+1]) of TokProgram.toff, M rows in all), nh heads of 32, K = nh * 32
   int nvid, Qv, nh;
   float scale;
   float* qkv;                  // (M, 3K) saved q | k | v (SAFWD writes, MHABWD reads)
-  float* probs;                // (nvid, nh, Qv, Qv) saved softmax
+  float* probs;                // (nvid, nh, Qv, Qv) saved softmax: a video's block dense (nh, Qv_v, Qv_v) inside
   unsigned attn_thr;
   float attn_scale;
   unsigned long long attn_seed;
@@ -74,6 +76,8 @@ struct TokPhase {
 struct TokProgram {
   TokPhase ph[TOK_MAXPH];
   int nphase, G;
+  int toff[TOK_MAXV + 1];      // token-row offsets of the attention items' videos (one table per program: the
+                               // phases are copied into registers whole, a table per phase would go with them)
   unsigned long long* bar;     // set by launch_tok
   unsigned* status;            // caller's status word (FX_STATUS_TOK_TIMEOUT)
   unsigned spin_max;

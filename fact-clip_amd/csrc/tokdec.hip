@@ -508,15 +508,16 @@ __device__ __forceinline__ void mm32s(const float* a, int lda, const float* b, i
 }
 
 // ------------------------------------------------------------------ self-attention forward item
-// (video v, head h), Qv <= 32 tokens, head dim 32: stage the video's rows (LN on load, this head's
+// (video v, head h), Qv <= 32 tokens (rows [toff[v], toff[v+1]) of the program's LDS table), head dim 32: stage the video's rows (LN on load, this head's
 // columns of the LN outputs written), v_h = x W_v,h^T + b from the staged rows, then (rows + query
 // position, added in place: (x + p) computed once, as a staged x + p would be) for q_h and k_h; each
 // product K-split over the 4 waves with every B load issued up front; then S = scale q k^T and
 // O = P_d V on the matrix cores, the row softmax (probabilities saved before the dropout) in between.
-__device__ __forceinline__ void safwd_phase(const TokPhase& P, float* lds, int G, unsigned long long* st) {
+__device__ __forceinline__ void safwd_phase(const TokPhase& P, const int* toff, float* lds, int G,
+                                            unsigned long long* st) {
   const int sit = (int)blockIdx.x + (st && st[7] == 3 ? G : 0);
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int nh = P.nh, Qv = P.Qv, A = P.K, nitems = P.nvid * nh;
+  const int nh = P.nh, Qm = P.Qv, A = P.K, nitems = P.nvid * nh;
   const int as = P.Kp + 4;
   float* As = lds;                                  // [32][as]
   float* red = As + 32 * as;                        // [3][4][16][64]
@@ -529,7 +530,8 @@ __device__ __forceinline__ void safwd_phase(const TokPhase& P, float* lds, int G
   const bool qpos = P.apos != nullptr;
   for (int it = blockIdx.x; it < nitems; it += G) {
     const int v = it / nh, h = it - v * nh;
-    const int R0 = v * Qv;
+    const int R0 = __builtin_amdgcn_readfirstlane(toff[v]);
+    const int Qv = __builtin_amdgcn_readfirstlane(toff[v + 1]) - R0;
     // every load of the item up front: the head's q / k / v weight fragments and the query-position
     // fragments (rows of this lane, its k range) that q and k add to the staged rows
     // (v weights and the position fragments before the staging, q / k weights after it: registers)
@@ -618,7 +620,7 @@ __device__ __forceinline__ void safwd_phase(const TokPhase& P, float* lds, int G
     }
     lds_sync();
     tstamp(it == sit ? st : nullptr, 5);
-    float* probs = P.probs + (long long)v * nh * Qv * Qv;
+    float* probs = P.probs + (long long)v * nh * Qm * Qm;   // the longest video's stride, dense inside
 #pragma unroll 1
     for (int i = w; i < 32; i += 4) {
       const float x = (lane < Qv && i < Qv) ? Ps[i * HS + lane] : -INFINITY;
@@ -629,9 +631,9 @@ __device__ __forceinline__ void safwd_phase(const TokPhase& P, float* lds, int G
       if (lane < Qv && i < Qv) {
         st1(probs + ((long long)h * Qv + i) * Qv + lane, p);   // saved before the dropout (the backward redraws it)
         pd = p;
-        if (P.attn_thr) {   // mha_small's mask: index (query_row * nh + h) * (nvid Qv) + key_row
-          const unsigned long long qg = (unsigned long long)v * Qv + i, kg = (unsigned long long)v * Qv + lane;
-          pd = p * keepf(P.attn_seed, P.attn_thr, P.attn_scale, (qg * nh + h) * ((unsigned long long)P.nvid * Qv) + kg);
+        if (P.attn_thr) {   // mha_small's mask: index (query_row * nh + h) * (all M token rows) + key_row
+          const unsigned long long qg = (unsigned long long)R0 + i, kg = (unsigned long long)R0 + lane;
+          pd = p * keepf(P.attn_seed, P.attn_thr, P.attn_scale, (qg * nh + h) * (unsigned long long)P.M + kg);
         }
       }
       if (lane < 32) Ps[i * HS + lane] = pd;
@@ -656,9 +658,9 @@ __device__ __forceinline__ void safwd_phase(const TokPhase& P, float* lds, int G
 // mha_small_bwd_kernel's algebra for one (video, head) on the matrix cores: dP = dO V^T (through the
 // dropout mask), dV = P_d^T dO, dS = P (dP - rowsum(P dP)), dq = scale dS K, dk = scale dS^T q
 // -> [dq | dk | dv] columns of the head.
-__device__ __forceinline__ void mhabwd_phase(const TokPhase& P, float* lds, int G) {
+__device__ __forceinline__ void mhabwd_phase(const TokPhase& P, const int* toff, float* lds, int G) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int nh = P.nh, Qv = P.Qv, A = P.K, nitems = P.nvid * nh;
+  const int nh = P.nh, Qm = P.Qv, A = P.K, nitems = P.nvid * nh;
   float* Qs = lds;
   float* Ks = Qs + 32 * HS;
   float* Vs = Ks + 32 * HS;
@@ -671,8 +673,9 @@ __device__ __forceinline__ void mhabwd_phase(const TokPhase& P, float* lds, int 
   const int c = lane & 31;
   for (int it = blockIdx.x; it < nitems; it += G) {
     const int v = it / nh, h = it - v * nh;
-    const int R0 = v * Qv;
-    const float* probs = P.probs + ((long long)v * nh + h) * Qv * Qv;
+    const int R0 = __builtin_amdgcn_readfirstlane(toff[v]);
+    const int Qv = __builtin_amdgcn_readfirstlane(toff[v + 1]) - R0;
+    const float* probs = P.probs + (long long)v * nh * Qm * Qm + (long long)h * Qv * Qv;
     lds_sync();
     {   // the head's q, k, v, dO and P tiles: 4 elements per thread each, every load issued first (clamped)
       float q4[4], k4[4], v4[4], d4[4], p4[4];
@@ -698,8 +701,8 @@ __device__ __forceinline__ void mhabwd_phase(const TokPhase& P, float* lds, int 
         Ps[i * HS + d] = pk ? p4[u] : 0.f;
         float kp = 1.f;
         if (drop && pk) {
-          const unsigned long long qg = (unsigned long long)v * Qv + i, kg = (unsigned long long)v * Qv + d;
-          kp = keepf(P.attn_seed, P.attn_thr, P.attn_scale, (qg * nh + h) * ((unsigned long long)P.nvid * Qv) + kg);
+          const unsigned long long qg = (unsigned long long)R0 + i, kg = (unsigned long long)R0 + d;
+          kp = keepf(P.attn_seed, P.attn_thr, P.attn_scale, (qg * nh + h) * (unsigned long long)P.M + kg);
         }
         Ms[i * HS + d] = kp;
       }
@@ -772,9 +775,11 @@ __global__ __launch_bounds__(TT) void tok_kernel(TokProgram prog) {
   static_assert(sizeof(TokPhase) % 4 == 0, "phase copy by words");
   constexpr int kPW = (int)(sizeof(TokPhase) / 4);
   __shared__ unsigned sph[TOK_MAXPH * kPW];
+  __shared__ int stoff[TOK_MAXV + 1];   // the attention items' token-row offsets (read per item)
   {
     const unsigned* src = reinterpret_cast<const unsigned*>(pk->ph);
     for (int i = threadIdx.x; i < prog.nphase * kPW; i += TT) sph[i] = src[i];
+    if (threadIdx.x <= TOK_MAXV) stoff[threadIdx.x] = pk->toff[threadIdx.x];
   }
   // diagnostic stamps (FX_TOK_DEBUG): kept in LDS (a global store at a phase start would put its
   // write acknowledgement in front of the phase's first wait), written out at the end
@@ -793,8 +798,8 @@ __global__ __launch_bounds__(TT) void tok_kernel(TokProgram prog) {
     __syncthreads();
     tstamp(st, 0);
     if (P.op == TOK_GEMM) gemm_phase(P, lds, prog.G, st);
-    else if (P.op == TOK_SAFWD) safwd_phase(P, lds, prog.G, st);
-    else if (P.op == TOK_MHABWD) mhabwd_phase(P, lds, prog.G);
+    else if (P.op == TOK_SAFWD) safwd_phase(P, stoff, lds, prog.G, st);
+    else if (P.op == TOK_MHABWD) mhabwd_phase(P, stoff, lds, prog.G);
     else if (P.op == TOK_LNROWS) ln_phase(P, prog.G);
     if (prog.debug) {
       __syncthreads();
@@ -840,6 +845,13 @@ int launch_tok(TokProgram& prog, hipStream_t s) {
     FX_REQUIRE(P.amode == TOK_A_PLAIN || P.K <= 256, "tok: LayerNorm rows of at most 256 columns");
     if (P.op == TOK_SAFWD || P.op == TOK_MHABWD)
       FX_REQUIRE(P.Qv >= 1 && P.Qv <= 32 && P.nh * 32 == P.K && P.K <= TOK_MAXSA, "tok: attention items need head dim 32, <= 32 tokens");
+    if (P.op == TOK_SAFWD || P.op == TOK_MHABWD) {
+      FX_REQUIRE(P.nvid >= 1 && P.nvid <= TOK_MAXV && prog.toff[0] == 0 && prog.toff[P.nvid] == P.M,
+                 "tok: the attention items' row offsets must span the phase's rows");
+      for (int v = 0; v < P.nvid; ++v)
+        FX_REQUIRE(prog.toff[v + 1] > prog.toff[v] && prog.toff[v + 1] - prog.toff[v] <= P.Qv,
+                   "tok: 1..Qv token rows per video");
+    }
   }
   static std::mutex mu;
   static std::map<std::pair<int, hipStream_t>, TokPool> pools;

@@ -516,7 +516,8 @@ __global__ __launch_bounds__(VT) void match_cost_kernel(const fx_video_attn* vid
       const float iou = den != 0.f ? ov[sg] / den : 0.f;
       c = -pc * prob[v.gl[sg]] - a2fc * iou;
     }
-    cost[((long long)vi * v.Q + a) * Gmax + sg] = c;
+    // (nvid, longest video's tokens = gridDim.x, Gmax): rows past a video's own tokens stay unwritten
+    cost[((long long)vi * gridDim.x + a) * Gmax + sg] = c;
   }
 }
 

@@ -1971,10 +1971,12 @@ class DecoderFn(torch.autograd.Function):
 
     @staticmethod
     def _set_call(prm, call):
-        """Per-call fields (dropout p's and seed, ragged memory offsets) of the cached param struct."""
+        """Per-call fields (dropout p's and seed, ragged memory / token offsets) of the cached param struct."""
         pd, pa, seed, mem_off = call[:4]
+        tok_off = call[5]
         prm.dropout, prm.attn_dropout, prm.seed = pd, pa, seed
         prm.mem_off = None if mem_off is None else ctypes.addressof(mem_off)
+        prm.tok_off = None if tok_off is None else ctypes.addressof(tok_off)
 
     @staticmethod
     def forward(ctx, tgt, qpos, mem, mpos, spec, nvid, call, *params):
@@ -2056,10 +2058,11 @@ class DecoderFn(torch.autograd.Function):
         return (dtgt, dqpos, dmem, dmpos, None, None, None) + tuple(t[1] for t in tg)
 
 
-def decoder(mod, tgt, memory=None, pos=None, query_pos=None, nvid=1, mem_off=None):
+def decoder(mod, tgt, memory=None, pos=None, query_pos=None, nvid=1, mem_off=None, tok_off=None):
     """Run an SCADecoder (memory given) or SADecoder through DecoderFn; returns (R, out_dim).
-    ``nvid`` videos stacked by rows: tokens split evenly, memory frames evenly or by the host prefix
-    list ``mem_off`` (ragged videos).  In training the layers' dropout runs inside the kernels
+    ``nvid`` videos stacked by rows: tokens split evenly or by the host prefix list ``tok_off`` (videos
+    with different token counts), memory frames evenly or by the host prefix list ``mem_off`` (ragged
+    videos).  In training the layers' dropout runs inside the kernels
     (counter-based masks from one drawn seed)."""
     spec = getattr(mod, "_fx_spec", None)
     if spec is None:
@@ -2077,7 +2080,8 @@ def decoder(mod, tgt, memory=None, pos=None, query_pos=None, nvid=1, mem_off=Non
     seed = dropout_seed() if (pd > 0 or pa > 0) else 0
     off = None if (mem_off is None or memory is None) else nx.int_array(mem_off)
     sink = _sink_of(query_pos) if qp is query_pos else None
-    return DecoderFn.apply(t2, qp, mem, mp, spec, int(nvid), (float(pd), float(pa), seed, off, sink), *params)
+    toff = None if tok_off is None else nx.int_array(tok_off)
+    return DecoderFn.apply(t2, qp, mem, mp, spec, int(nvid), (float(pd), float(pa), seed, off, sink, toff), *params)
 
 
 # ---------------------------------------------------------------------------

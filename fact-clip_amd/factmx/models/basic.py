@@ -400,10 +400,17 @@ class SCADecoder(nn.Module):
         self.num_layers = num_layers
         self.norm = norm
 
-    def forward(self, tgt, memory, pos: Optional[Tensor] = None, query_pos: Optional[Tensor] = None):
+    def forward(self, tgt, memory, pos: Optional[Tensor] = None, query_pos: Optional[Tensor] = None,
+                mem_off=None, tok_off=None):
+        """``tok_off`` (and ``mem_off``): host prefix lists of stacked videos' token (frame-memory) rows --
+        one call for videos of different token counts (fused kernel path only)."""
         out = _as3d(fxf.linear(tgt, self.in_linear.weight, self.in_linear.bias)) if self.in_map else tgt
         if _fused_decoder_ok(self):
-            return _as3d(fxf.decoder(self, out, memory, pos=pos, query_pos=query_pos))
+            nvid = 1 if tok_off is None else len(tok_off) - 1
+            return _as3d(fxf.decoder(self, out, memory, pos=pos, query_pos=query_pos, nvid=nvid, mem_off=mem_off,
+                                     tok_off=tok_off))
+        if tok_off is not None or mem_off is not None:
+            raise NotImplementedError("stacked videos need the fused decoder kernel path")
         for layer in self.layers:
             out = layer(out, memory, pos=pos, query_pos=query_pos)
         if self.norm is not None:
@@ -426,10 +433,14 @@ class SADecoder(nn.Module):
         self.num_layers = num_layers
         self.norm = norm
 
-    def forward(self, tgt, pos: Optional[Tensor] = None):
+    def forward(self, tgt, pos: Optional[Tensor] = None, tok_off=None):
+        """``tok_off``: host prefix list of stacked videos' token rows (fused kernel path only)."""
         out = _as3d(fxf.linear(tgt, self.in_linear.weight, self.in_linear.bias)) if self.in_map else tgt
         if _fused_decoder_ok(self):
-            return _as3d(fxf.decoder(self, out, None, pos=None, query_pos=pos))
+            nvid = 1 if tok_off is None else len(tok_off) - 1
+            return _as3d(fxf.decoder(self, out, None, pos=None, query_pos=pos, nvid=nvid, tok_off=tok_off))
+        if tok_off is not None:
+            raise NotImplementedError("stacked videos need the fused decoder kernel path")
         for layer in self.layers:
             out = layer(out, out, out, query_pos=pos, key_pos=pos, value_pos=pos)
         if self.norm is not None:

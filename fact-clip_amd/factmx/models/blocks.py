@@ -218,9 +218,9 @@ def _save_views(blk, vb, f_cl, a_cl, a_feat=None, seg=None, attn=None):
     segment class logits); ``attn``: (f2a logits, f2a attention, a2f logits, a2f attention) over the
     segments if ``seg`` is given, else over the frames.  Video v's record holds frame_clogit (T, 1, C),
     action_clogit (Q, 1, C + 1), action_feature (Q, 1, A), seg_clogit (S, 1, C) and tdu, f2a_attn(_logit)
-    (1, Q, n) and a2f_attn(_logit) (1, n, Q) with n = S or T, each as far as given.  Returns the records:
-    a family rewrites them where its attributes differ."""
-    Q, n = vb.Q, vb.Ts
+    (1, Q, n) and a2f_attn(_logit) (1, n, Q) with n = S or T, each as far as given (Q: the video's own token
+    count, vb.Qs[v]).  Returns the records: a family rewrites them where its attributes differ."""
+    Qs, n = vb.Qs, vb.Ts
     bt = dict(f_cl=f_cl, a_cl=a_cl)
     fc, ac = vb.frames(f_cl), vb.tokens(a_cl)
     if a_feat is not None:
@@ -232,7 +232,7 @@ def _save_views(blk, vb, f_cl, a_cl, a_feat=None, seg=None, attn=None):
         bt.update(seg_cl=seg_cl, S=n, s_off=sg["s_off"], local=sg["local"])
     if attn is not None:
         f2a_lg, f2a_at, a2f_lg, a2f_at = attn
-        qn = [Q * k for k in n]
+        qn = [q * k for q, k in zip(Qs, n)]
         fat, aat, flg, alg = (torch.split(t, qn) for t in (f2a_at, a2f_at, f2a_lg, a2f_lg))
         bt.update(f2a_lg=f2a_lg, a2f_lg=a2f_lg, a2f_at=a2f_at)
     recs = []
@@ -243,7 +243,7 @@ def _save_views(blk, vb, f_cl, a_cl, a_feat=None, seg=None, attn=None):
         if seg is not None:
             rec.update(seg_clogit=sc[v].unsqueeze(1), tdu=basic.TemporalDownsampleUpsample(*sg["local"][v]))
         if attn is not None:
-            k = n[v]
+            k, Q = n[v], Qs[v]
             rec.update(f2a_attn=fat[v].view(1, Q, k), a2f_attn=aat[v].view(1, k, Q),
                        f2a_attn_logit=flg[v].view(1, Q, k), a2f_attn_logit=alg[v].view(1, k, Q))
         recs.append(rec)
@@ -297,7 +297,7 @@ class InputBlock(Block):
                 a = fxf.linear(a, br.out_map.weight, br.out_map.bias)
         else:
             a = fxf.decoder(br, a2, f_out, pos=fpos, query_pos=apos, nvid=vb.nvid,
-                            mem_off=vb.f_off if vb.ragged else None)
+                            mem_off=vb.f_off if vb.ragged else None, tok_off=vb.tok_off)
         a_out, a_cl = fxf.process_feature(a, self.nclass + 1)
         _save_views(self, vb, f_cl, a_cl, (a_out, self.nclass + 1))
         return f_out, a_out
@@ -342,7 +342,7 @@ class UpdateBlock(Block):
         f2a, a2f = self.f2a_layer, self.a2f_layer
         a, f2a_lg, f2a_at = fxf.x2y(f2a, f2, a2, fpos if f2a.kq_pos else None, apos if f2a.kq_pos else None,
                                     rows=(vb.f_off, vb.a_off))
-        a = fxf.decoder(self.action_branch, a, None, query_pos=apos, nvid=vb.nvid)
+        a = fxf.decoder(self.action_branch, a, None, query_pos=apos, nvid=vb.nvid, tok_off=vb.tok_off)
         a_out, a_cl = fxf.process_feature(a, self.nclass + 1)
         f, a2f_lg, a2f_at = fxf.x2y(a2f, a_out, f2, apos if a2f.kq_pos else None, fpos if a2f.kq_pos else None,
                                     rows=(vb.a_off, vb.f_off))
@@ -438,7 +438,7 @@ class _TDU:
         f2a, a2f = self.f2a_layer, self.a2f_layer
         a, f2a_lg, f2a_at = fxf.x2y(f2a, seg_out, a2, seg_pos if f2a.kq_pos else None, apos if f2a.kq_pos else None,
                                     rows=(s_off, vb.a_off))
-        a = fxf.decoder(self.action_branch, a, None, query_pos=apos, nvid=vb.nvid)
+        a = fxf.decoder(self.action_branch, a, None, query_pos=apos, nvid=vb.nvid, tok_off=vb.tok_off)
         a_out, a_cl = self.heads.split_tokens(a)
         sgf, a2f_lg, a2f_at = fxf.x2y(a2f, a_out, seg_out, apos if a2f.kq_pos else None,
                                       seg_pos if a2f.kq_pos else None, rows=(vb.a_off, s_off))
@@ -613,13 +613,14 @@ class _FACTBase(nn.Module):
         """All videos through the blocks in lockstep (see _forward_videos); returns restore(v), which
         points every side-channel attribute at video v's views.  ``on_a2f`` (vloss.EarlyMatch,
         vn_vloss.BatchMatch) runs when the last block's token logits and token -> frame (segment)
-        attention exist.  ``transcripts`` (FACT.trans): per video its host class list, all of one length N;
-        the tokens are then their embedded entries (fxf.token_embed with the action_pe rows, blocks.py:75-79),
-        N per video, and carry no position (the reference passes zeros)."""
+        attention exist.  ``transcripts`` (FACT.trans): per video its host class list; the tokens are then
+        their embedded entries (fxf.token_embed with the action_pe rows, blocks.py:75-79), as many per video as
+        its transcript has (lengths may differ: the token rows are then ragged, _VideoBatch.tok_off), and
+        carry no position (the reference passes zeros)."""
         nvid = len(seq_list)
         if transcripts is not None:
-            Q = len(transcripts[0])
-            assert Q >= 1 and all(len(t) == Q for t in transcripts), "one pass takes transcripts of one length"
+            Q = [len(t) for t in transcripts]
+            assert min(Q) >= 1, "empty transcript"
         else:
             Q = self.cfg.FACT.ntoken
         vb = _VideoBatch(nvid, [int(s.shape[0]) for s in seq_list], Q)
@@ -640,10 +641,11 @@ class _FACTBase(nn.Module):
         fpos = None if fpe[0] is None else torch.cat([p.squeeze(1) for p in fpe], 0)
         if transcripts is not None:
             vb.transcripts = [np.asarray(t, dtype=np.int32) for t in transcripts]
-            if Q > self.action_pe.pe.shape[0]:
-                self.action_pe(torch.empty(Q, 0))          # (grows the table, as PositionalEncoding.forward)
+            if max(Q) > self.action_pe.pe.shape[0]:
+                self.action_pe(torch.empty(max(Q), 0))     # (grows the table, as PositionalEncoding.forward)
+            # (token positions restart at 0 in every video)
             a2 = fxf.token_embed(self.action_embed.weight, np.concatenate(vb.transcripts), self.action_pe.pe,
-                                 np.tile(np.arange(Q, dtype=np.int32), nvid))
+                                 np.concatenate([np.arange(q, dtype=np.int32) for q in Q]))
             # The reference passes zero query positions for a transcript input (blocks.py:79).  None would
             # save the adds, and fx_decoder_* / fx_x2y_* have a branch for a NULL position, but no test of the
             # suite runs the decoders' branch (every fixture and layer test gives positions), so a zero tensor
@@ -808,17 +810,26 @@ def _sum_terms(terms):
 
 class _VideoBatch:
     """Row layout of nvid videos stacked for one batched pass: frames of video v are rows
-    [f_off[v], f_off[v+1]) (lengths Ts, ragged allowed), its action tokens rows [v*Q, (v+1)*Q).
-    T is the common length of an equal-length batch (None when ragged)."""
+    [f_off[v], f_off[v+1]) (lengths Ts, ragged allowed), its action tokens rows [a_off[v], a_off[v+1]).
+    T is the common length of an equal-length batch (None when ragged).  ``Q``: tokens per video, an int
+    or a per-video list (transcript tokens); ``Qs`` is the list either way, ``Q`` the common count -- not
+    to be read when the counts differ (``tok_ragged``; it raises), and ``tok_off`` is then ``a_off``, the
+    decoders' token-row offsets (None for an even split)."""
 
     def __init__(self, nvid, Ts, Q):
-        self.nvid, self.Ts, self.Q = nvid, list(Ts), Q
+        self.nvid, self.Ts = nvid, list(Ts)
+        self.Qs = [int(q) for q in Q] if isinstance(Q, (list, tuple)) else [int(Q)] * nvid
+        assert len(self.Qs) == nvid
+        self.tok_ragged = len(set(self.Qs)) > 1
         self.ragged = len(set(self.Ts)) > 1
         self.T = None if self.ragged else self.Ts[0]
         self.f_off = [0]
         for T in self.Ts:
             self.f_off.append(self.f_off[-1] + T)
-        self.a_off = [v * Q for v in range(nvid + 1)]
+        self.a_off = [0]
+        for q in self.Qs:
+            self.a_off.append(self.a_off[-1] + q)
+        self.tok_off = self.a_off if self.tok_ragged else None
         # the loss phase's hooks (set by the model): on_a2f(vb, token logits, a2f attention[, segments]) runs in
         # block ``last``, before sf_merge or after the frame branch is issued (_TDU.forward_batch)
         self.on_a2f = self.last = self.while_waiting = None
@@ -828,8 +839,22 @@ class _VideoBatch:
     def fr(self, v):
         return slice(self.f_off[v], self.f_off[v + 1])
 
+    @property
+    def Q(self):
+        if self.tok_ragged:
+            raise AttributeError("_VideoBatch.Q: the videos' token counts differ (read Qs / a_off)")
+        return self.Qs[0]
+
     def tk(self, v):
-        return slice(v * self.Q, (v + 1) * self.Q)
+        return slice(self.a_off[v], self.a_off[v + 1])
+
+    def attn_off(self, n):
+        """Prefix offsets of the packed per-video (token, row) attention blocks, video v having n[v] rows
+        (frames or segments): fxf.x2y packs each video's Qs[v] * n[v] block in video order."""
+        off = [0]
+        for q, k in zip(self.Qs, n):
+            off.append(off[-1] + q * k)
+        return off
 
     # Per-video chunks through ONE split node per tensor: its backward concatenates the chunks'
     # gradients once, where per-video slicing costs a zero-filled full-size tensor, a copy and an
@@ -838,7 +863,7 @@ class _VideoBatch:
         return torch.split(t, self.Ts, dim=0)
 
     def tokens(self, t):
-        return torch.split(t, self.Q, dim=0)
+        return torch.split(t, self.Qs, dim=0)
 
 
 # lockstep batches take the loss phase through models/vloss.py (False: per-video MatchCriterion ops)
@@ -847,6 +872,10 @@ FUSED_LOSS = True
 # transcript-conditioned models (FACT.trans) take the lockstep pass and the fused loss phase (False: every
 # video alone through _run_blocks and the per-video MatchCriterion ops; A/B runs)
 TRANS_BATCH = True
+
+# a transcript batch of unequal lengths as ONE lockstep pass with ragged token rows (fx_decoder_params.tok_off).
+# Off by default: the grouping of transcript_passes below is what the suite's transcript tests pin.
+TRANS_RAGGED = False
 
 
 MAX_LOCKSTEP_VIDEOS = 16   # ragged frame-branch convs carry at most 16 video offsets per launch
@@ -871,11 +900,12 @@ def _batchable(net, seq_list):
 
 
 def transcript_passes(transcripts):
-    """How the videos of a transcript batch share lockstep passes: the decoders split the stacked token rows
-    evenly, so a batch whose transcripts all have one length (a batch of one included) is ONE pass; any
-    other batch runs every video as its own pass of one video.  Returns the passes as lists of video indices."""
+    """How the videos of a transcript batch share lockstep passes.  A batch whose transcripts all have one
+    length (a batch of one included) is ONE pass; any other batch runs every video as its own pass of one
+    video -- unless TRANS_RAGGED is on: then any batch of at most MAX_LOCKSTEP_VIDEOS videos is one pass, its
+    token rows ragged.  Returns the passes as lists of video indices."""
     n = len(transcripts)
-    if len({len(t) for t in transcripts}) <= 1:
+    if len({len(t) for t in transcripts}) <= 1 or (TRANS_RAGGED and n <= MAX_LOCKSTEP_VIDEOS):
         return [list(range(n))] if n else []
     return [[v] for v in range(n)]
 
@@ -1014,7 +1044,8 @@ def _forward_transcript_videos(net, seq_list, label_list, hosts, compute_loss):
         if k:       # the previous pass's read-back leaves the pinned buffers the next pass reuses (vloss._pinned)
             vloss.resolve_pending()
         seqs = [seq_list[v] for v in vids]
-        early = vloss.EarlyMatch(net, [hosts[v] for v in vids], Q=len(transcripts[vids[0]])) if compute_loss else None
+        early = vloss.EarlyMatch(net, [hosts[v] for v in vids], Q=[len(transcripts[v]) for v in vids]) \
+            if compute_loss else None
         restore = net._forward_batch(seqs, early, [transcripts[v] for v in vids])
         restore(len(vids) - 1)
         for i, v in enumerate(vids):

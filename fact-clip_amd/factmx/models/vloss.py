@@ -208,7 +208,8 @@ def resolve_pending():
 def _stage2_labels(net, labs, G, Q):
     """Stage 2's tables that depend on the labels only (EarlyMatch.prepare): the holdout remap and the
     per-video InfoNCE targets (blocks.py:677-747), and the term table's host arrays -- token targets and
-    matched-column slots (capacity G[v] >= K), filled after the matching -- in the pack sent with it."""
+    matched-column slots (capacity G[v] >= K), filled after the matching -- in the pack sent with it.
+    ``Q``: per video its token count."""
     from .blocks import FACT_CLIP
     cfg = net.cfg
     nvid = len(labs)
@@ -243,7 +244,7 @@ def _stage2_labels(net, labs, G, Q):
         y_con.append(y)
     pk2 = _Pack()
     # per video: token targets (Q) and the matched columns (capacity G[v] >= K), filled after matching
-    tgt_arr = [np.full(Q, C1 - 1, dtype=np.int32) for _ in range(nvid)]
+    tgt_arr = [np.full(Q[v], C1 - 1, dtype=np.int32) for v in range(nvid)]
     tgt_off = [pk2.array(t, np.int32) for t in tgt_arr]
     tgt_arr = [pk2.items[-nvid + v][1] for v in range(nvid)]     # the buffers pk2 sends
     kcap = [max(int(G[v]), 1) for v in range(nvid)]
@@ -281,8 +282,10 @@ class EarlyMatch:
 
     def __init__(self, net, hosts, Q=None):
         self.net, self.hosts = net, hosts
-        # tokens per video: the learned queries, or (FACT.trans) the transcript length of the pass
-        self.Q = int(net.cfg.FACT.ntoken if Q is None else Q)
+        # tokens per video: the learned queries, or (FACT.trans) the transcript lengths of the pass (an int
+        # or a per-video list)
+        Q = net.cfg.FACT.ntoken if Q is None else Q
+        self.Qs = [int(q) for q in Q] if isinstance(Q, (list, tuple)) else [int(Q)] * len(hosts)
         self.done = False
         self.prepared = False
 
@@ -313,14 +316,17 @@ class EarlyMatch:
         pk.send()
         self.__dict__.update(labs=labs, gts=gts, G=G, Gmax=max(G), gt_off=gt_off, lab_off=lab_off, cw=cw,
                              cw_off=cw_off, pk=pk, base=base)
-        self.stage2 = _stage2_labels(net, labs, G, self.Q)
+        self.stage2 = _stage2_labels(net, labs, G, self.Qs)
         self.prepared = True
 
     def __call__(self, vb, a_cl, a2f_at, seg=None):
         net, cfg = self.net, self.net.cfg
         lib = nx.load()
-        nvid, Q, fo = vb.nvid, vb.Q, vb.f_off
-        assert Q == self.Q, (Q, self.Q)
+        nvid, Qs, fo, ao = vb.nvid, vb.Qs, vb.f_off, vb.a_off
+        assert Qs == self.Qs, (Qs, self.Qs)
+        Qmax = max(Qs)
+        # (a2f attention: per video its packed (rows, tokens) block over the segments (seg = (s_off, local)) or frames)
+        at = vb.attn_off([seg[0][v + 1] - seg[0][v] for v in range(nvid)] if seg is not None else vb.Ts)
         C1 = net.num_classes + 1
         dev = a_cl.device
         self.prepare(dev)
@@ -330,20 +336,19 @@ class EarlyMatch:
         vbase = pkv.alloc(dev)
         for v in range(nvid):
             a = va[v]
+            Q = Qs[v]
             a.Q, a.C1, a.T, a.G = Q, C1, vb.Ts[v], G[v]
-            a.clogit, a.ldc = _ptr_rows(a_cl, v * Q, C1), C1
+            a.clogit, a.ldc = _ptr_rows(a_cl, ao[v], C1), C1
+            a.attn, a.lda = a2f_at.data_ptr() + 4 * at[v], Q
             if seg is not None:
-                s_off, local = seg
-                a.attn, a.lda = a2f_at.data_ptr() + 4 * Q * s_off[v], Q
-                a.seg_id = local[v][0].data_ptr()
-            else:
-                a.attn, a.lda = a2f_at.data_ptr() + 4 * Q * fo[v], Q
+                a.seg_id = seg[1][v][0].data_ptr()
             a.gs, a.ge, a.gl = (base + o for o in gt_off[v])
             a.pred_off = fo[v]
         pkv.send()
         self.cost_host = None
         if cfg.Loss.match != "seq":
-            cost = torch.empty(nvid * Q * Gmax, dtype=torch.float32, device=dev)
+            # (nvid, Qmax, Gmax): rows past a video's own tokens are neither written nor read
+            cost = torch.empty(nvid * Qmax * Gmax, dtype=torch.float32, device=dev)
             nx.check(lib.fx_match_cost(ctypes.addressof(va), vbase + va_off, nvid, float(cfg.Loss.pc),
                                        float(cfg.Loss.a2fc), Gmax, nx.ptr(cost), nx.stream()), "fx_match_cost")
             self.cost_host = _pinned("cost", cost.shape, torch.float32)
@@ -354,20 +359,22 @@ class EarlyMatch:
         self.pkv = pkv
         self.done = True
 
-    def matches(self, Q):
-        """Hungarian / one-to-many / sequential matching per video (loss.py:108-193) on the host."""
+    def matches(self, Q=None):
+        """Hungarian / one-to-many / sequential matching per video (loss.py:108-193) on the host, on the
+        (nvid, longest video's tokens, Gmax) cost block (``Q``: unused, the counts are self.Qs)."""
         kind = self.net.cfg.Loss.match
         cost = None
         if self.cost_host is not None:
             self.cost_ready.synchronize()
-            cost = self.cost_host.numpy().reshape(len(self.G), Q, self.Gmax)
+            cost = self.cost_host.numpy().reshape(len(self.G), max(self.Qs), self.Gmax)
         out = []
         for v, Gv in enumerate(self.G):
+            Q = self.Qs[v]
             if kind == "seq":
                 assert Q >= Gv, (Q, Gv)
                 ai = si = np.arange(Gv)
             else:
-                c = cost[v, :, :Gv].astype(np.float64)
+                c = cost[v, :Q, :Gv].astype(np.float64)
                 if not np.isfinite(c).all():
                     # costs from a step whose kernels reported a failure (e.g. a BiGRU timeout): raise that
                     # failure (the status word is final: the costs' event has completed) rather than the
@@ -393,7 +400,7 @@ def run(net, vb, compute_loss, early=None):
     cfg = net.cfg
     blocks = list(net.block_list)
     last = blocks[-1]._bt
-    nvid, Q, Ts, fo = vb.nvid, vb.Q, vb.Ts, vb.f_off
+    nvid, Qs, Ts, fo, ao = vb.nvid, vb.Qs, vb.Ts, vb.f_off, vb.a_off
     C = net.num_classes
     C1 = C + 1
     dev = last["f_cl"].device
@@ -412,17 +419,17 @@ def run(net, vb, compute_loss, early=None):
     def eval_structs(pk, gl=None):
         """``gl``: per video the device address of its transcript (the transcript prediction reads it)."""
         off, va = pk.structs(nx.VideoAttn, nvid)
+        at = vb.attn_off(last["S"] if "S" in last else Ts)
         for v in range(nvid):
             a = va[v]
+            Q = Qs[v]
             a.Q, a.C1, a.T = Q, C1, Ts[v]
             if gl is not None:
                 a.G, a.gl = Q, gl[v]
-            a.clogit, a.ldc = _ptr_rows(last["a_cl"], v * Q, C1), C1
+            a.clogit, a.ldc = _ptr_rows(last["a_cl"], ao[v], C1), C1
+            a.attn, a.lda = last["a2f_at"].data_ptr() + 4 * at[v], Q
             if "S" in last:
-                a.attn, a.lda = last["a2f_at"].data_ptr() + 4 * Q * last["s_off"][v], Q
                 a.seg_id = last["local"][v][0].data_ptr()
-            else:
-                a.attn, a.lda = last["a2f_at"].data_ptr() + 4 * Q * fo[v], Q
             a.flogit, a.ldf = _ptr_rows(flog, fo[v], C), C
             a.pred_off = fo[v]
         return off, va
@@ -436,7 +443,7 @@ def run(net, vb, compute_loss, early=None):
         base = pk.alloc(dev)
         if trans_pred:
             for v in range(nvid):
-                va[v].G, va[v].gl = Q, base + tr_off[v]
+                va[v].G, va[v].gl = Qs[v], base + tr_off[v]
         pk.send()
         nx.check(eval_fn(ctypes.addressof(va), base + va_off, nvid, float(cfg.FACT.mwt), nx.ptr(pred), nx.stream()),
                  eval_name)
@@ -468,8 +475,8 @@ def run(net, vb, compute_loss, early=None):
     _stamp("con")
     # the predictions (no matching needed): own small table, launched before the wait
     pke = _Pack()
-    if trans_pred and any(G[v] != Q for v in range(nvid)):
-        raise RuntimeError(f"vloss: transcript lengths {G} of a pass with {Q} token rows per video")
+    if trans_pred and any(G[v] != Qs[v] for v in range(nvid)):
+        raise RuntimeError(f"vloss: transcript lengths {G} of a pass with {Qs} token rows per video")
     # (a video's ground-truth class list in the label tables IS its transcript)
     va_off, va = eval_structs(pke, [base + gt_off[v][2] for v in range(nvid)] if trans_pred else None)
     pke.alloc(dev)
@@ -526,15 +533,16 @@ def run(net, vb, compute_loss, early=None):
             if is_tdu:
                 seg_cl = bt["seg_cl"]
                 psg = seg_cl.data_ptr()
+            at = vb.attn_off(bt["S"] if is_tdu else Ts)
         for v in range(nvid):
             gs, ge, gl = gt_off[v]
-            T = Ts[v]
+            T, Q = Ts[v], Qs[v]
             # frame CE (+ smooth) on the block's frame logits
             t = term(k, v, nx.TERM_CLASS, T, C, pf + 4 * fo[v] * C, C, 1, f_cl, fo[v] * C, fce / T,
                      (sw_coef / ((T - 1) * C) if sw_coef and T > 1 else 0.0))
             t.y, t.w = base + lab_off[v], cw_p
             # token CE (c_ce = 1 / the targets' class-weight sum, after the matching)
-            t = term(k, v, nx.TERM_CLASS, Q, C1, pa + 4 * v * Q * C1, C1, 1, a_cl, v * Q * C1, 0.0, 0.0)
+            t = term(k, v, nx.TERM_CLASS, Q, C1, pa + 4 * ao[v] * C1, C1, 1, a_cl, ao[v] * C1, 0.0, 0.0)
             t.y, t.w = base2 + tgt_off[v], cw_p
             tok_terms.append((t, v))
             if isinstance(blk, InputBlock):
@@ -546,10 +554,10 @@ def run(net, vb, compute_loss, early=None):
                 rs, re = bt["local"][v][1].data_ptr(), bt["local"][v][2].data_ptr()
                 t = term(k, v, nx.TERM_CLASS, Sv, C, psg + 4 * s0 * C, C, 1, seg_cl, s0 * C, 0.5 / Sv, 0.0)
                 t.rs, t.re, t.gs, t.ge, t.gl, t.G, t.w = rs, re, base + gs, base + ge, base + gl, G[v], cw_p
-                R, off, c_xe, c_sm = Sv, Q * s0, 1.0 / Sv, 0.0
+                R, off, c_xe, c_sm = Sv, at[v], 1.0 / Sv, 0.0
             else:
                 rs = re = None
-                R, off = T, Q * fo[v]
+                R, off = T, at[v]
                 c_xe, c_sm = 1.0 / T, (sw_coef / ((T - 1) * Q) if sw_coef and T > 1 else 0.0)
             # f2a logits (Q, R) read as (R, Q): log_softmax over rows per matched column (dim=1)
             for x, g, sr, sc, axis in ((pfa, f2a, 1, R, 0), (paf, a2f, Q, 1, 1)):
@@ -582,7 +590,7 @@ def run(net, vb, compute_loss, early=None):
     _stamp("structs")
 
     # ------------------------------------------------------------------ the matching (waits for the costs)
-    matches = early.matches(Q)
+    matches = early.matches(Qs)     # (the argument is unused: the counts are early.Qs)
     _stamp("matches")
     big = [v for v, (ai, _) in enumerate(matches) if len(ai) > nx.LOSS_MAXK]
     if big:      # e.g. o2m matching (every ground-truth segment paired, loss.py:155-193) past 512 segments

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define FX_ABI_VERSION 27
+#define FX_ABI_VERSION 28
 
 enum {
   FX_OK = 0,
@@ -211,7 +211,7 @@ int fx_x2y_bwd(const float* X, long long ldx, int Nx, int xdim, int xpos_cols, c
  * separate q (A,A), k (A,Hm), v (A,Hm) weights with the packed (3A) in_proj_bias.
  * Shapes: tgt (R, A) ld, qpos (R, A) dense or NULL, mem (T, Hm) ld, mpos (T, Hm) or
  * NULL, out (R, out_dim).  nvid videos stacked by rows: video v owns token rows
- * [v*R/nvid, (v+1)*R/nvid) and memory rows [v*T/nvid, (v+1)*T/nvid) (or mem_off); attention
+ * [v*R/nvid, (v+1)*R/nvid) (or tok_off) and memory rows [v*T/nvid, (v+1)*T/nvid) (or mem_off); attention
  * never crosses videos, every projection runs over all rows at once.
  * bwd: every weight gradient ACCUMULATES (+=) into g; dtgt, dqpos (dense (R,A)),
  * dmem, dmpos are written (each nullable; dqpos accumulated when dqpos_accumulate).
@@ -249,6 +249,11 @@ typedef struct fx_decoder_params {
                                  wait gives up (outputs then wrong; never cleared by the library) */
   int dqpos_accumulate;       /* bwd: dqpos += instead of = (a position gradient shared with other ops,
                                  as fx_x2y_bwd has_xpos bit 1) */
+  const int* tok_off;         /* host (nvid + 1) token-row offsets of videos with different token counts:
+                                 increasing, tok_off[0] = 0, tok_off[nvid] = R (>= 1 token per video); NULL:
+                                 video v owns token rows [v R/nvid, (v+1) R/nvid).  Set it before asking
+                                 fx_decoder_saved_floats / fx_decoder_workspace_floats: per-video blocks are
+                                 sized by the longest video */
 } fx_decoder_params;
 
 typedef struct fx_decoder_grads {
@@ -899,7 +904,8 @@ int fx_loss_terms_bwd(const fx_loss_term* terms_host, const fx_loss_term* terms_
  * their classes gl, G of them.
  * fx_match_cost (MatchCriterion.match, loss.py:108-153 + a2f_soft_iou 91-106):
  *   cost[v, a, s] = -pc * softmax(clogit[a])[gl[s]] - a2fc * overlap / union,
- *   (nvid, Q, Gmax), s >= G_v zero-filled.
+ *   (nvid, Q, Gmax) with Q the largest token count of the videos, s >= G_v zero-filled,
+ *   rows a >= Q_v of a video with fewer tokens left unwritten.
  * fx_eval_pred (Block._eval / eval_with_clip, blocks.py:243-261, 854-887):
  *   pred[pred_off + t] = argmax((1-mwt) softmax(clogit[best token of t])[:C] +
  *   mwt softmax(flogit[t])), or argmax(softmax(flogit[t])) when every token is null.
