@@ -60,7 +60,8 @@ struct WsBound {
   const float* prev_lo;
   const float* prev_hi;
 };
-// The library's side stream (one per device; FX_SIDE_STREAM=0: none).  side_fork: the side stream
+// The library's side stream (runtime.cpp; one per device; FX_SIDE_STREAM=0: none).  Entry points use it through
+// SideLane (ops.h); decoder.cpp through these two.  side_fork: the side stream
 // (after making it wait for everything enqueued on s so far), or s itself when there is none;
 // side_join_into: s waits for everything enqueued on the side stream.
 hipStream_t side_fork(hipStream_t s, int event);
@@ -70,7 +71,7 @@ int side_join_into(hipStream_t s);
 hipStream_t aux_fork(hipStream_t s);
 int aux_join_into(hipStream_t s, hipStream_t a);
 // split-K factor for weight-gradient GEMMs deferred to the side stream over `rows` rows (keeps each
-// workgroup's share of K short, so the main stream's kernels find free CUs)
+// workgroup's share of K short, so the main stream's kernels find free CUs)   (linear.cpp)
 int defer_split(int rows);
 // workspace floats needed by a split-K descriptor
 long long gemm_workspace_floats(const fx_gemm_desc& d);
@@ -118,7 +119,7 @@ int launch_dropout(const float* x, long long ldx, int rows, int cols, long long 
 // A/B switches of the default paths (FX_GEMM_PATH, FX_GEMM_W8, FX_GEMM_WIDE, FX_GEMM_XCDPLANES, FX_GEMM_GROUP,
 // FX_SIDE_STREAM, FX_MSTCN_DEFER, the fused-kernel switches below): read from the environment ONCE, at the
 // library's first use, into this
-// table (std::call_once); no entry point reads the environment itself.  Defaults are the tuned paths.
+// table (std::call_once, runtime.cpp); no entry point reads the environment itself.  Defaults are the tuned paths.
 struct Knobs {
   int gemm_path = 0;        // 1 tiled, 2 direct (0: the planner's choice)
   bool gemm_w8 = true;      // 8-wave 128x64 tiles
@@ -152,7 +153,7 @@ struct Knobs {
 };
 const Knobs& knobs();
 
-// event-based timing hooks around launches of one kernel class (bench roofline): prof_begin / prof_end
+// event-based timing hooks around launches of one kernel class (bench roofline; runtime.cpp): prof_begin / prof_end
 // bracket a call (HIP events on the stream: kernels + any host-issue gap between them), and every kernel
 // launched through fx_launch while a bracket is open on this thread also gets its OWN event pair through
 // hipExtLaunchKernel, whose timestamps are the kernel's execution (the rocprofv3 kernel-trace duration)

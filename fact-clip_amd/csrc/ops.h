@@ -1,4 +1,6 @@
-// Internal (non-ABI) declarations shared by the factmx translation units.
+// Internal (non-ABI) declarations shared by the factmx translation units: the kernel files' launchers and
+// the composite helpers of the host files (runtime.cpp, linear.cpp); frames.h adds what only the two MS-TCN
+// files share.
 #pragma once
 #include "fx_common.h"
 
@@ -131,7 +133,21 @@ int launch_x2y_a2f_bwd(const float* dfeat, long long ldf, const float* xv, const
                        const float* dattn, const float* dlogit_in, int Hd, float scale, int nvid, const int* yoff,
                        const int* xoff, const long long* aoff, float* dlogit, float* dyq, hipStream_t s);
 
-// ---- composite helpers (capi.cpp) --------------------------------------------
+// ---- composite helpers (runtime.cpp, linear.cpp) -------------------------------
+// One entry point's use of the library's side stream (runtime.cpp): weight-gradient GEMMs that nothing
+// downstream reads run on `side` while the input-gradient chain goes on on `main`.  Without a side stream
+// (FX_SIDE_STREAM=0, or side_lane(main, false)) side == main and every call is a no-op.
+struct SideStream;
+struct SideLane {
+  hipStream_t main, side;
+  SideStream* ss;
+  int fork(int e) const;          // side waits for main's work so far (fork event e: 0 .. 2)
+  int done(int i) const;          // side: layer i's work is enqueued (event i & 3)
+  int wait(int i) const;          // main waits for the side stream's layer i
+  int join(bool deferred) const;  // main waits for all of side, unless the caller joins later (fx_side_join)
+};
+SideLane side_lane(hipStream_t main, bool on = true);
+
 int ew_grid(long long total);
 int relu_bwd(const float* dy, long long lddy, const float* y, long long ldy, int rows, int cols, float* dz,
              long long lddz, hipStream_t s);

@@ -233,22 +233,65 @@ def test_linear_padded_k_on_wider_input(M, K, N):
     _close(bd.grad, br.grad, rtol=1e-4, atol=1e-4, what="db")
 
 
+def _prof_count(lib, kind):
+    ms, fl, by, n = ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_int()
+    assert lib.fx_prof_collect(kind, ctypes.byref(ms), ctypes.byref(fl), ctypes.byref(by), ctypes.byref(n)) == 0
+    return n.value
+
+
+def _skewed_grads(mod):
+    """.grad of every parameter as a view into ONE buffer in parameter order, with a 64-float gap after
+    layer 1's parameters: layer 2 does not sit one layer stride after layer 1, so the per-layer gradient
+    pointers are not uniformly strided and the deferred batched weight gradients cannot address them."""
+    named = [(n_, p) for n_, p in mod.named_parameters() if p.requires_grad]
+    last1 = max(i for i, (n_, _) in enumerate(named) if n_.startswith("layers.1."))
+    flat = torch.zeros(sum(p.numel() for _, p in named) + 64, device=named[0][1].device)
+    off = 0
+    for i, (_, p) in enumerate(named):
+        p.grad = flat[off:off + p.numel()].view_as(p)
+        off += p.numel() + (64 if i == last1 else 0)
+    return flat
+
+
 @pytest.mark.parametrize("fused", ["0", "1"])
 @pytest.mark.parametrize("T,nvid,nl", [(1000, 2, 10), (4096, 1, 3), (37, 3, 4), ((1000, 777, 1301), 3, 10),
                                        ((64, 5, 200), 3, 4)])
 def test_mstcn_fused_layers_match_fp64(T, nvid, nl, fused, monkeypatch):
+    _mstcn_fused_layers_case(T, nvid, nl, fused, "separate", monkeypatch)
+
+
+@pytest.mark.parametrize("fused", ["0", "1"])
+@pytest.mark.parametrize("grads", ["flat", "skewed"])
+@pytest.mark.parametrize("T,nvid,nl", [(37, 3, 4), ((64, 5, 200), 3, 4)])
+def test_mstcn_backward_schedules_match_fp64(T, nvid, nl, grads, fused, monkeypatch):
+    """The four backward schedules of fx_mstcn_bwd, each chosen on purpose, at the smallest shapes that run
+    the fused layer (F = 256): grads "flat" (FlatGradReducer: uniformly strided, the deferred schedules) or
+    "skewed" (_skewed_grads: not uniformly strided, the per-layer schedules), with and without the fused
+    layer kernel.  fx_prof kind 7 counts the fused-layer launches: nl forward and nl - 1 backward (the bottom
+    layer's conv backward is a GEMM) with the fused kernel, none without."""
+    _mstcn_fused_layers_case(T, nvid, nl, fused, grads, monkeypatch)
+
+
+def _mstcn_fused_layers_case(T, nvid, nl, fused, grads, monkeypatch):
     """F = 256, both MS-TCN paths: the two-GEMM layers and (fx_mstcn_params.fused_layers) the fused
     layer kernel (mstcn_fused.hip) forward + fused dX chain backward: output, input gradient and every
     weight gradient vs the float64 MS-TCN restatement (odd row counts, dilations up to 2^(nl-1),
     several videos: no leakage across video edges).  A tuple T is a ragged batch (row offsets through
     the conv GEMMs and the fused layer's tap gather, up to 16 videos; the deferred weight gradients in
     one launch per weight kind, the ragged frame lookup in the GEMM's B loader over K = rows rounded up
-    to the 64-deep stage)."""
+    to the 64-deep stage).  grads: "separate" = gradients allocated by the backward (ragged batches: the
+    flat buffer), "flat" / "skewed" as in test_mstcn_backward_schedules_match_fp64."""
     from factmx.dp import FlatGradReducer
     from factmx.models.basic import MSTCN
     monkeypatch.setattr(fxf, "MSTCN_FUSED_LAYERS", 2 if fused == "1" else 0)   # 2: the fused kernel at any size
+    lib = nx.load()
     torch.manual_seed(0)
     mod = MSTCN(96, 256, 40, nl, dropout=0.0, ln=False, in_map=True).to(DEV).train()
+    if grads == "flat" or (grads == "separate" and isinstance(T, tuple)):
+        FlatGradReducer(mod.parameters())        # uniformly strided gradients: the deferred batched dW path
+    elif grads == "skewed":
+        flat = _skewed_grads(mod)
+        assert all(flat.data_ptr() <= p.grad.data_ptr() < flat.data_ptr() + 4 * flat.numel() for p in mod.parameters())
     Ts = list(T) if isinstance(T, tuple) else [T] * nvid
     off = [0]
     for t_ in Ts:
@@ -257,13 +300,22 @@ def test_mstcn_fused_layers_match_fp64(T, nvid, nl, fused, monkeypatch):
     x = _r(rows, 96, seed=11)
     g = _r(rows, 40, seed=12)
     xd = x.float().to(DEV).requires_grad_(True)
-    if isinstance(T, tuple):
-        FlatGradReducer(mod.parameters())        # uniformly strided gradients: the deferred batched dW path
-        y = fxf.mstcn(mod, xd, T=0, nvid=nvid, seq_off=off)
-    else:
-        y = fxf.mstcn(mod, xd, T=T, nvid=nvid)
-    saved = y.grad_fn.saved_tensors[1].detach().double().cpu()   # (freed by the backward)
-    (y * g.float().to(DEV)).sum().backward()
+    assert lib.fx_prof_enable(7, 64) == 0
+    try:
+        if isinstance(T, tuple):
+            y = fxf.mstcn(mod, xd, T=0, nvid=nvid, seq_off=off)
+        else:
+            y = fxf.mstcn(mod, xd, T=T, nvid=nvid)
+        n_fwd = _prof_count(lib, 7)
+        saved = y.grad_fn.saved_tensors[1].detach().double().cpu()   # (freed by the backward)
+        assert lib.fx_prof_enable(7, 64) == 0
+        (y * g.float().to(DEV)).sum().backward()
+        torch.cuda.synchronize()
+        n_bwd = _prof_count(lib, 7)
+    finally:
+        lib.fx_prof_disable()
+    assert n_fwd == (nl if fused == "1" else 0), n_fwd
+    assert n_bwd == (nl - 1 if fused == "1" else 0), n_bwd
     # the float64 restatement takes the GPU's own ReLU decisions (z > 0 of the saved activations):
     # a pre-activation within ~1e-6 of 0 may land on the other side in fp32 (either summation order
     # is valid), which would move single dZ entries -- whole conv-weight-gradient rows -- by O(1)
