@@ -1043,7 +1043,7 @@ int fx_decoder_bwd(const fx_decoder_params* p, const fx_decoder_grads* g, const 
       FX_TRY(kind(1, NL - 1, dq0 + 3 * RA + 2 * A, 3 * A, 3 * RA, b0 + L.t3, A, PL, A, A, g->sa_in_w, g->sa_in_b,
                   2 * A, 2LL * A * A));
     }
-    for (size_t i = 0; i < pend.size(); i += 4)   // 4: members per grouped launch (gemm_f32.hip GMAX)
+    for (size_t i = 0; i < pend.size(); i += 4)   // 4: members per grouped launch (gemm_dev.h GMAX)
       FX_TRY(launch_gemm_group(pend.data() + i, (int)std::min<size_t>(4, pend.size() - i), sd));
   }
   {

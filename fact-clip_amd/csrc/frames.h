@@ -30,7 +30,7 @@ inline int check_seqs(const Seqs& q) {
 }
 
 // dilated-conv operand over the call's videos (zero outside each video).  The column-major (weight-
-// gradient) form of a ragged call needs K padded to whole 64-deep stages (gemm_f32.hip COLS_CONVR): the
+// gradient) form of a ragged call needs K padded to whole 64-deep stages (gemm_dev.h COLS_CONVR): the
 // per-layer weight gradients (K = rows) run video by video instead.
 inline fx_operand conv_operand(const float* h, long long ld, int cin, int dil, int dir, const Seqs& q, bool trans) {
   fx_operand o = trans ? op_cols(h, ld) : op_rows(h, ld);

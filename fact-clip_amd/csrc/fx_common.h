@@ -116,13 +116,12 @@ inline unsigned long long fx_drop_subseed(unsigned long long seed, int i) {
 int launch_dropout(const float* x, long long ldx, int rows, int cols, long long idx_ld, long long idx_col0, float p,
                    unsigned long long seed, float* y, long long ldy, hipStream_t s);
 
-// A/B switches of the default paths (FX_GEMM_PATH, FX_GEMM_W8, FX_GEMM_WIDE, FX_GEMM_XCDPLANES, FX_GEMM_GROUP,
+// A/B switches of the default paths (FX_GEMM_PATH, FX_GEMM_WIDE, FX_GEMM_XCDPLANES, FX_GEMM_GROUP,
 // FX_SIDE_STREAM, FX_MSTCN_DEFER, the fused-kernel switches below): read from the environment ONCE, at the
 // library's first use, into this
 // table (std::call_once, runtime.cpp); no entry point reads the environment itself.  Defaults are the tuned paths.
 struct Knobs {
   int gemm_path = 0;        // 1 tiled, 2 direct (0: the planner's choice)
-  bool gemm_w8 = true;      // 8-wave 128x64 tiles
   int gemm_wide = -1;       // 0 / 1 force the 128x64 tiles off / on (-1: the planner's choice)
   bool gemm_xcd_planes = true;
   bool gemm_persist = true;  // FX_GEMM_PERSIST=0: one workgroup per wide8 tile (A/B)

@@ -307,7 +307,7 @@ int MstcnBwd::batched_dw() const {
     FX_TRY(launch_gemm(d, lane.side));
   }
   {   // dilated conv: dW_i += dZ_i^T taps(h_i) stored straight into (F, F, 3)   (batched over layers;
-      // ragged videos in the same launch: the B loader finds each frame's video, gemm_f32.hip COLS_CONVR)
+      // ragged videos in the same launch: the B loader finds each frame's video, gemm_dev.h COLS_CONVR)
     fx_operand b = conv_operand(h(0), F, F, dil(0), 1, q, true);
     b.batch_stride = L.rowsF;
     fx_operand a = op_cols(dZall(0), F);

@@ -6,7 +6,7 @@
 
 namespace fx {
 
-// ---- kernels (rowops.hip, segments.hip, gru.hip, gemm_f32.hip, attn_small.hip) ----
+// ---- kernels (rowops.hip, segments.hip, gru.hip, gemm_*.hip, attn_small.hip) ----
 long long colsum_workspace_floats(int M, int N);
 int launch_layernorm_fwd(const float* x, long long ldx, const float* r, long long ldr, const float* w,
                          const float* b, float eps, int rows, int cols, int relu, float* y, long long ldy,

@@ -122,7 +122,6 @@ const Knobs& knobs() {
   std::call_once(once, [] {
     auto env = [](const char* n) -> const char* { return std::getenv(n); };
     if (const char* p = env("FX_GEMM_PATH")) k.gemm_path = std::string(p) == "tiled" ? 1 : std::string(p) == "direct" ? 2 : 0;
-    if (const char* p = env("FX_GEMM_W8")) k.gemm_w8 = p[0] == '1';
     if (const char* p = env("FX_GEMM_WIDE")) k.gemm_wide = p[0] == '1' ? 1 : 0;
     if (const char* p = env("FX_GEMM_XCDPLANES")) k.gemm_xcd_planes = p[0] != '0';
     if (const char* p = env("FX_GEMM_GROUP")) k.gemm_group = p[0] != '0';

@@ -14,7 +14,7 @@ using namespace fx;
 // logit / attn hold each video's (ny_v x nx_v) block, packed in video order.
 // saved: xin (Nx*xdim, X+Xpos when Xpos), yin (Ny*ydim), xk, xv (Nx*Hd), yq, feat (Ny*Hd)
 namespace {
-constexpr int GMAX_GROUP = 4;   // members of one grouped direct-GEMM launch (gemm_f32.hip GMAX)
+constexpr int GMAX_GROUP = 4;   // members of one grouped direct-GEMM launch (gemm_dev.h GMAX)
 struct X2YLayout {
   long long xin, yin, xk, xv, yq, feat, total;
 };

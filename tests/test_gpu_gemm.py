@@ -96,6 +96,135 @@ def test_gemm_fused_bias_column(M, K, split):
     torch.testing.assert_close(dbd.double().cpu(), db + dy.sum(0), rtol=1e-5, atol=atol)
 
 
+# ---------------------------------------------------------------- every (family, A kind, B kind) a plan can reach
+# Operand forms (csrc/gemm_dev.h Kind): rows / cols = plain row- / column-major, conv = implicit 3-tap dilated
+# conv (row-major A: ROWS_CONV, column-major B: COLS_CONV), cat = two sources side by side (ROWS_CAT), gen = rows
+# plus a positional add (ROWS_GEN, the generic element fetch).  "+u" pads the leading dimension by one float, so
+# the operand is not 16-B vector-loadable and the launch takes the generic loaders.
+def _f32(*shape, seed, scale=1.0):
+    return _r(*shape, seed=seed, scale=scale).float().double()   # float64 holding exactly the fp32 inputs
+
+
+def _im2col(X, dil, seq_len):
+    """(R, cin) -> (R, 3 cin): column j cin + c of row r is X[r + (j - 1) dil, c], zero outside r's video."""
+    R, cin = X.shape
+    out = torch.zeros(R, 3 * cin, dtype=X.dtype)
+    for s in range(0, R, seq_len):
+        e = min(R, s + seq_len)
+        for j in range(3):
+            sh = (j - 1) * dil
+            lo, hi = max(s, s - sh), min(e, e - sh)
+            if hi > lo:
+                out[lo:hi, j * cin:(j + 1) * cin] = X[lo + sh:hi + sh]
+    return out
+
+
+def _dev(X, unaligned):
+    """fp32 device copy of a 2-d float64 matrix, its leading dimension one float longer when `unaligned`."""
+    buf = torch.zeros(X.shape[0], X.shape[1] + int(unaligned), device=DEV)
+    buf[:, :X.shape[1]] = X.float().to(DEV)
+    return buf
+
+
+def _make(form, R, K, seed):
+    """Operand of R rows over K in the given form: (fx_operand, its (R, K) float64 value, tensors to keep)."""
+    kind, _, flag = form.partition("+")
+    u = flag == "u"
+    o = nx.Operand()
+    o.conv_dir = 1
+    if kind in ("rows", "gen"):
+        X = _f32(R, K, seed=seed)
+        keep = [_dev(X, u)]
+        o.ptr, o.ld = nx.ptr(keep[0]), keep[0].shape[1]
+        if kind == "gen":
+            pc = min(K, 40)
+            pos = _f32(R, pc, seed=seed + 50)
+            keep.append(pos.float().to(DEV).contiguous())
+            o.pos, o.ld_pos, o.pos_cols = nx.ptr(keep[1]), pc, pc
+            X = X.clone()
+            X[:, :pc] += pos
+        return o, X, keep
+    if kind == "cols":
+        X = _f32(R, K, seed=seed)
+        keep = [_dev(X.t().contiguous(), u)]
+        o.ptr, o.ld, o.trans = nx.ptr(keep[0]), keep[0].shape[1], 1
+        return o, X, keep
+    if kind == "cat":
+        ks = 64
+        X = _f32(R, K, seed=seed)
+        keep = [_dev(X[:, :ks].contiguous(), u), _dev(X[:, ks:].contiguous(), u)]
+        o.ptr, o.ld, o.ptr1, o.ld1, o.k_split = nx.ptr(keep[0]), keep[0].shape[1], nx.ptr(keep[1]), keep[1].shape[1], ks
+        return o, X, keep
+    raise AssertionError(form)
+
+
+def _make_conv(R, cin, seq_len, dil, trans, u, seed):
+    X = _f32(R, cin, seed=seed)
+    keep = [_dev(X, u)]
+    o = nx.Operand()
+    o.ptr, o.ld, o.trans, o.conv_dir = nx.ptr(keep[0]), keep[0].shape[1], int(trans), 1
+    o.conv_taps, o.conv_cin, o.conv_dil, o.seq_len = 3, cin, dil, seq_len
+    return o, _im2col(X, dil, seq_len), keep
+
+
+# shapes by family, from the planner's thresholds: wide8 from 192 tiles of 128 x 64 with K % 64 == 0; below that
+# and past 512 tiles of 32 x 32 the 64 x 64 tiled kernel; token rows (M = 32) the direct kernel.  A conv A has
+# K = 3 cin (cin 64), a conv B has N = 3 cin.
+WIDE, TILED, SMALL = (1536, 1024), (768, 768), (32, 96)
+PAIR_CASES = (
+    # the 128 x 64 f32 kernel
+    [("wide8", a, b, WIDE, "fp32") for a, b in [("rows", "conv"), ("conv", "cols"), ("conv", "conv"), ("cat", "cols"),
+                                                 ("cat", "conv"), ("cols", "rows")]]
+    # the precision modes on the same tile: bf16 kernel, split kernel (B cols) / register split (B rows)
+    + [("prec", a, b, WIDE, p) for p in ("bf16", "fp32s", "fp32s2") for a in ("rows", "conv", "cat")
+       for b in ("rows", "cols")]
+    # the 64 x 64 kernel, FAST loaders
+    + [("tiled", a, b, TILED, "fp32") for a, b in [("rows", "conv"), ("conv", "cols"), ("conv", "conv"),
+                                                   ("cat", "cols"), ("cat", "conv"), ("cols", "rows")]]
+    # the 64 x 64 kernel, generic loaders: B not vector-loadable, or a positional add on either side
+    + [("generic", a, b, TILED, "fp32") for a in ("rows", "conv", "gen", "cols", "cat")
+       for b in ("rows+u", "cols+u", "conv+u", "gen")]
+    # the direct kernel's pairs the model's shapes leave out
+    + [("direct", a, b, SMALL, "fp32") for a, b in [("gen", "cols"), ("cat", "cols"), ("cols", "rows")]]
+)
+
+
+@pytest.mark.parametrize("family,aform,bform,MN,prec", PAIR_CASES,
+                         ids=[f"{f}-{a}-{b}-{p}" for f, a, b, _, p in PAIR_CASES])
+def test_gemm_family_pairs(family, aform, bform, MN, prec):
+    """One launch per (kernel family, A kind, B kind) that the planner can reach and the model's own shapes
+    in this suite do not, at the smallest shape that selects the family, against float64 torch.  fp32 and
+    the 3-piece split keep the file's fp32 tolerance; bf16 rounds both operands to 8 significant bits
+    (each within 2^-9, so a product within 2^-8) and the 2-piece split keeps 16 (~2^-16 per product): those
+    two add that fraction of |A| |B|, the bound of the number format."""
+    M, N = MN
+    K = 192 if aform.startswith("conv") else 128
+    if bform.startswith("conv"):
+        N = N // 3 // 8 * 8 * 3   # 3 taps of cin channels, cin % 8 == 0 (1008 still gives the wide kernel 192 tiles)
+    if aform.startswith("conv"):
+        a, A, ka = _make_conv(M, 64, 256, 3, False, aform.endswith("+u"), seed=21)
+    else:
+        a, A, ka = _make(aform, M, K, seed=21)
+    if bform.startswith("conv"):
+        b, Bt, kb = _make_conv(K, N // 3, 64, 2, True, bform.endswith("+u"), seed=22)   # (K, N) value
+    else:
+        b, Bn, kb = _make(bform, N, K, seed=22)
+        Bt = Bn.t()
+    ref = A @ Bt
+    c = torch.empty(M, N, device=DEV)
+    with fxf.gemm_precision(prec):
+        fxf.gemm(M, N, K, a, b, c, N)
+    torch.cuda.synchronize()
+    err = (c.double().cpu() - ref).abs()
+    tol = 1e-5 * (1 + ref.abs().max().item()) + 1e-6 * K ** 0.5
+    print(f"{family} {aform} x {bform} {prec}: max err {err.max().item():.3e} (fp32 tolerance {tol:.3e})")
+    if prec in ("bf16", "fp32s2"):
+        bound = ((1 + 2.0 ** -9) ** 2 - 1 if prec == "bf16" else 2.0 ** -16) * (A.abs() @ Bt.abs()) + tol
+        assert bool((err <= bound).all()), (err - bound).max().item()
+    else:
+        assert err.max().item() <= tol, err.max().item()
+
+
 def test_split_k_repeat_is_deterministic():
     """The per-tile arrival counters re-arm: back-to-back split-K launches give identical bits."""
     A = _r(3000, 64, seed=11).float().to(DEV)

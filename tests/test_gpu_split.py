@@ -1,5 +1,5 @@
 """FX_PREC_F32S: fp32 GEMM arithmetic on the bf16 matrix cores (3-piece bf16 split of every fp32
-operand, 6 piece products summed in the fp32 accumulator; gemm_f32.hip gemm_split_wide8_kernel).
+operand, 6 piece products summed in the fp32 accumulator; gemm_split.hip gemm_split_wide8_kernel).
 
 Checked against the float64 product of the SAME fp32 inputs, next to the native f32-MFMA kernel on
 the same shapes: the split kernel's error must stay at fp32 level (within 2x the native kernel's

@@ -19,7 +19,7 @@ CATS = [  # (category, substrings of the kernel name), first match wins
     ("x2y cores", ["x2y_"]),
     ("small MHA", ["mha_small"]),
     ("direct GEMM (token rows)", ["gemm_direct"]),
-    ("frame GEMM wide8", ["gemm_f32_wide8", "gemm_f32_wide_kernel", "gemm_bf16", "gemm_split"]),
+    ("frame GEMM wide8", ["gemm_f32_wide8", "gemm_bf16", "gemm_split"]),
     ("tiled GEMM 64x64", ["gemm_f32_kernel"]),
     ("split-K reduce", ["splitk_reduce"]),
     ("LayerNorm", ["ln_fwd", "ln_bwd", "ln_param"]),
