@@ -12,8 +12,14 @@ namespace {
 struct Mstcn2Layout {
   long long rowsF;
   long long f, cat, r, wb1, wb2, total_saved;            // saved: f_0..f_L, cat_i (2F), r_i, dX-packed weights
-  long long wf1, wf2, hb0, hb1, du, dcat, spm, spl, bsl, total_ws;
+  long long wf1, wf2, hb0, hb1, du, dcat, spm, spl, bsl, wk, total_ws;
 };
+
+// the fused layer kernel (mstcn2_fused.hip) can serve stacks of this shape: what the size functions reserve for
+// (whether a call takes it also depends on its rows, videos, buffers and stream: mstcn2_fused_ok)
+bool mstcn2_fused_shape(const fx_mstcn2_params* p) { return p->fused_layers && p->F == 256 && p->ngroup <= 1; }
+// fragment-order weights of one fused pass: per layer two conv matrices (3 F F each) and the fusion matrix (2 F F)
+long long mstcn2_frag_floats(int F) { return 2 * frl_packed_floats(3 * F) + frl_packed_floats(2 * F); }
 
 Mstcn2Layout mstcn2_layout(const fx_mstcn2_params* p, int rows) {
   Mstcn2Layout L{};
@@ -49,7 +55,10 @@ Mstcn2Layout mstcn2_layout(const fx_mstcn2_params* p, int rows) {
     sb = std::max(sb, split_ws(F, 3 * F + 1, rows, nb));
   }
   if (ng > 1) sb = std::max(sb, gconv_dw_ws_floats(rows, p->F, ng));   // grouped conv dW partials
-  L.total_ws = L.bsl + sb;
+  // fused layers: this pass's weights in MFMA fragment order (the forward's three matrices per layer, or the
+  // backward chain's -- each call packs its own, so a backward never depends on what the forward ran)
+  L.wk = al64(L.bsl + sb);
+  L.total_ws = mstcn2_fused_shape(p) ? L.wk + NL * mstcn2_frag_floats(p->F) : L.bsl + sb;
   return L;
 }
 
@@ -59,6 +68,17 @@ int mstcn2_dil(const fx_mstcn2_params* p, int e) {   // dil_factor^e
   for (int k = 0; k < e; ++k) d *= f;
   return (int)d;
 }
+
+// Whether the fused layer kernel serves this call, `buf` being the buffer of row slots it would read.
+// fx_mstcn2_fwd and fx_mstcn2_bwd each ask for themselves.  The bf16 / split precision modes exist for their
+// arithmetic: a stream in one of them keeps its GEMM kernels.
+bool mstcn2_fused_ok(const fx_mstcn2_params* p, const Seqs& q, const float* buf, hipStream_t s) {
+  return mstcn2_fused_shape(p) && frl_supported(p->F, buf, p->F, 2 * p->F) && (!q.off || q.nvid <= 16) &&
+         fx_get_stream_precision(s) == FX_PREC_F32 &&
+         (p->fused_layers == 2 || frl_fills_device(q.rows(), knobs().frl2_min_fill));
+}
+
+constexpr int kProfFrl2 = 15;   // fx_prof kind of the fused MS-TCN++ layer chains
 
 }  // namespace
 }  // namespace fx
@@ -96,7 +116,31 @@ int fx_mstcn2_fwd(const fx_mstcn2_params* p, const float* x, long long ldx, int 
     FX_CHECK_HIP(hipMemcpy2DAsync(f0, F * sizeof(float), x, ldx * sizeof(float), F * sizeof(float), rows,
                                   hipMemcpyDeviceToDevice, s));
   }
-  for (int i = 0; i < NL; ++i) {
+  const bool fused = NL > 0 && mstcn2_fused_ok(p, q, saved, s) && frl_supported(F, ws + L.wk, F, F);
+  if (fused) {   // the conv images packed above and W_fu as given, in fragment order: one pack launch
+    const long long c3 = frl_packed_floats(3 * F), per = mstcn2_frag_floats(F);
+    std::vector<FragJob> J;
+    for (int i = 0; i < NL; ++i) {
+      float* wk = ws + L.wk + i * per;
+      J.push_back({ws + L.wf1 + i * c3, wk, 3 * F, 3 * F});
+      J.push_back({ws + L.wf2 + i * c3, wk + c3, 3 * F, 3 * F});
+      J.push_back({p->w_fu[i], wk + 2 * c3, 2 * F, 2 * F});
+    }
+    for (size_t j = 0; j < J.size(); j += FRAG_JOBS)
+      FX_TRY(launch_pack_frag(J.data() + j, (int)std::min<size_t>(FRAG_JOBS, J.size() - j), s));
+    // cat_i, r_i and f_i+1 of every layer: one kernel per layer (timed as one chain, like kind 7)
+    prof_begin(kProfFrl2, s);
+    for (int i = 0; i < NL; ++i) {
+      const float* wk = ws + L.wk + i * per;
+      const Frl2Layer y{rows, T, mstcn2_dil(p, NL - 1 - i), mstcn2_dil(p, i), q.off, q.nvid,
+                        i != NL - 1 ? p->dropout : 0.f, fx_drop_subseed(p->seed, i)};
+      FX_TRY(launch_frl2_fwd(y, saved + L.f + i * L.rowsF, wk, wk + c3, p->b_d1[i], p->b_d2[i],
+                             saved + L.cat + 2 * i * L.rowsF, wk + 2 * c3, p->b_fu[i], saved + L.r + i * L.rowsF,
+                             saved + L.f + (i + 1) * L.rowsF, s));
+    }
+    prof_end(kProfFrl2, s, NL * 2.0 * rows * F * 8.0 * F, NL * 4.0 * (5.0 * rows * F + 8.0 * F * F), NL);
+  }
+  for (int i = 0; i < NL && !fused; ++i) {
     const float* fi = saved + L.f + i * L.rowsF;
     float* fn = saved + L.f + (i + 1) * L.rowsF;
     float* cat = saved + L.cat + 2 * i * L.rowsF;
@@ -167,21 +211,55 @@ int fx_mstcn2_bwd(const fx_mstcn2_params* p, const fx_mstcn2_grads* g, const flo
   float* Hb[2] = {ws + L.hb0, ws + L.hb1};
   float* gF = Hb[0];
   FX_TRY(linear_dx(dy, lddy, p->w_out, rows, F, p->cout, gF, F, 0, nullptr, 0, spm, s));
+  // Fused chain (mstcn2_fused.hip): the top layer's dU / dCat and the bottom layer's two conv GEMMs stay as
+  // below; in between, ONE kernel per layer forms G_i, dU_i-1 and dCat_i-1.  Its fragment-order weights are
+  // packed here from the forward's dX images in `saved` and from W_fu, whatever path the forward took.
+  const bool fchain = NL > 1 && mstcn2_fused_ok(p, q, ws + L.hb0, s) && frl_supported(F, ws + L.wk, F, F);
+  const long long c3 = frl_packed_floats(3 * F), per = mstcn2_frag_floats(F);
+  if (fchain) {
+    std::vector<FragJob> J;
+    for (int i = 0; i < NL; ++i) {
+      float* wk = ws + L.wk + i * per;
+      if (i >= 1) {   // conv^T of layers L-1 .. 1
+        J.push_back({saved + L.wb1 + i * c3, wk, 3 * F, 3 * F});
+        J.push_back({saved + L.wb2 + i * c3, wk + c3, 3 * F, 3 * F});
+      }
+      if (i < NL - 1)   // the halves of W_fu^T of layers L-2 .. 0
+        for (int h = 0; h < 2; ++h) J.push_back({p->w_fu[i] + h * F, wk + 2 * c3 + (long long)h * F * F, 2 * F, F, 1});
+    }
+    for (size_t j = 0; j < J.size(); j += FRAG_JOBS)
+      FX_TRY(launch_pack_frag(J.data() + j, (int)std::min<size_t>(FRAG_JOBS, J.size() - j), s));
+  }
   for (int i = NL - 1; i >= 0; --i) {
     const float* ri = saved + L.r + i * L.rowsF;
     float* dU = ws + L.du + i * L.rowsF;
     float* dCat = ws + L.dcat + 2 * i * L.rowsF;
-    // dU = dropout_i(gF) * (r_i > 0)   (r_i is stored after the dropout: zero where dropped)
-    if (i != NL - 1 && p->dropout > 0.f) {
-      FX_TRY(launch_dropout(gF, F, rows, F, F, 0, p->dropout, fx_drop_subseed(p->seed, i), dU, F, s));
-      FX_TRY(relu_bwd(dU, F, ri, F, rows, F, dU, F, s));
-    } else {
-      FX_TRY(relu_bwd(gF, F, ri, F, rows, F, dU, F, s));
-    }
-    // dCat = dU . W_fu   (rows x 2F)
-    FX_TRY(launch_gemm(gemm_desc(rows, 2 * F, F, op_rows(dU, F), op_cols(p->w_fu[i], 2 * F), dCat, 2 * F), s));
-    // dF_i = gF + conv_d1^T(dA) + conv_d2^T(dB)
     float* dFn = Hb[(NL - i) & 1];
+    if (!(fchain && i < NL - 1)) {   // (fused chain: layer i + 1's step left dU_i and dCat_i in their slots)
+      // dU = dropout_i(gF) * (r_i > 0)   (r_i is stored after the dropout: zero where dropped)
+      if (i != NL - 1 && p->dropout > 0.f) {
+        FX_TRY(launch_dropout(gF, F, rows, F, F, 0, p->dropout, fx_drop_subseed(p->seed, i), dU, F, s));
+        FX_TRY(relu_bwd(dU, F, ri, F, rows, F, dU, F, s));
+      } else {
+        FX_TRY(relu_bwd(gF, F, ri, F, rows, F, dU, F, s));
+      }
+      // dCat = dU . W_fu   (rows x 2F)
+      FX_TRY(launch_gemm(gemm_desc(rows, 2 * F, F, op_rows(dU, F), op_cols(p->w_fu[i], 2 * F), dCat, 2 * F), s));
+    }
+    if (fchain && i >= 1) {   // G_i, dU_i-1 and dCat_i-1 in one kernel
+      if (i == NL - 1) prof_begin(kProfFrl2, s);   // (the chain of NL - 1 back-to-back launches timed as one)
+      const Frl2Layer y{rows, T, mstcn2_dil(p, NL - 1 - i), mstcn2_dil(p, i), q.off, q.nvid, p->dropout,
+                        fx_drop_subseed(p->seed, i - 1)};
+      FX_TRY(launch_frl2_bwd(y, dCat, ws + L.wk + i * per, ws + L.wk + i * per + c3, gF, dFn,
+                             saved + L.r + (i - 1) * L.rowsF, ws + L.du + (i - 1) * L.rowsF,
+                             ws + L.wk + (i - 1) * per + 2 * c3, ws + L.dcat + 2 * (i - 1) * L.rowsF, s));
+      if (i == 1)
+        prof_end(kProfFrl2, s, (NL - 1) * 2.0 * rows * F * 8.0 * F, (NL - 1) * 4.0 * (7.0 * rows * F + 8.0 * F * F),
+                 NL - 1);
+      gF = dFn;
+      continue;
+    }
+    // dF_i = gF + conv_d1^T(dA) + conv_d2^T(dB)
     for (int h = 0; h < 2; ++h) {
       const int dil = h == 0 ? mstcn2_dil(p, NL - 1 - i) : mstcn2_dil(p, i);
       if (ng > 1) {   // grouped: conv_d1's pass writes gF + conv^T(dA), conv_d2's adds conv^T(dB)
@@ -210,7 +288,7 @@ int fx_mstcn2_bwd(const fx_mstcn2_params* p, const fx_mstcn2_grads* g, const flo
   // gradient buffers are uniformly strided (views of one flat buffer), else one launch per layer
   FX_TRY(lane.fork(1));
   if (NL > 0) {
-    WsBound wbb(ws + L.bsl, L.total_ws - L.bsl);
+    WsBound wbb(ws + L.bsl, L.wk - L.bsl);
     const bool uni = uniform_stride(g->w_fu, NL) && uniform_stride(g->b_fu, NL) && uniform_stride(g->w_d1, NL) &&
                      uniform_stride(g->b_d1, NL) && uniform_stride(g->w_d2, NL) && uniform_stride(g->b_d2, NL);
     const int growth = p->dil_factor > 0 ? p->dil_factor : 2;

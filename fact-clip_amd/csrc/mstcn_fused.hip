@@ -28,26 +28,20 @@
 #include <map>
 #include <mutex>
 
+#include "frl_dev.h"
 #include "fx_common.h"
 #include "ops.h"
 
 namespace fx {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-constexpr int FR = 32;           // rows per workgroup
-constexpr int FN = 256;          // channels: N of both GEMMs, K of the second
-constexpr int FBK = 32;          // k per stage
-constexpr int FT = 512;          // threads: 8 waves x 32 columns
-constexpr int AS = FBK + 4;      // LDS row stride of the activation stage images ([row][k], k contiguous)
+using namespace frl_dev;   // tile geometry, fragment loads, MFMA stage, tile order
+
 constexpr int VS = FN + 4;       // LDS row stride of the phase-1 tile
-constexpr int A_IMG = FR * AS;
-constexpr int NSL = 3;           // activation ring depth
 // weight fragments are loaded PD = 3 stages ahead of their use into NB = PD + 1 register sets (kernel
 // template parameter; 5 measured no faster)
 constexpr int LDS_FLOATS = NSL * A_IMG + FR * VS;
 constexpr int LDS_FLOATS_PAIR = 2 * NSL * A_IMG + FR * VS;
-constexpr int kMaxSeqF = 16;     // ragged videos per launch
 
 struct FrlArgs {
   const float* x;      // phase-1 conv operand rows (M, FN), ld ldx
@@ -96,33 +90,6 @@ __device__ unsigned long long g_frl_st[1024 * 8];
   } while (0)
 #endif
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-
-// packed weight fragment of stage st, wave w for this lane: 4 float4 (k = 16 lh + 4 q .. + 3)
-__device__ __forceinline__ void load_b(const float* wp, int st, int w, int lane, float4* b) {
-  const float* base = wp + ((long long)(st * 8 + w) * 4) * 256 + lane * 4;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) b[q] = ld4(base + q * 256);
-}
-
-// A fragments of one 32-deep stage from LDS rows `a` (row stride as): lane (li, lh) takes row li, k 16 lh ..
-__device__ __forceinline__ void lds_frag(const float* a, int as, int li, int lh, float4* fa) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) fa[q] = ld4(a + li * as + lh * 16 + q * 4);
-}
-
-// the 16 MFMAs of one stage from fragments already in registers
-__device__ __forceinline__ void mma_frag(const float4* fa, const float4* fb, f32x16& acc) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[q].x, fb[q].x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[q].y, fb[q].y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[q].z, fb[q].z, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[q].w, fb[q].w, acc, 0, 0, 0);
-  }
-}
-
 // 16 MFMAs of one 32-deep stage: A rows from `a` (row stride as), B = this wave's fragments; the
 // lane pairs A[li][16 lh + s] with B[n][16 lh + s]
 __device__ __forceinline__ void mma_stage(const float* a, int as, const float4* fb, int li, int lh, f32x16& acc) {
@@ -138,23 +105,8 @@ __device__ __forceinline__ void mma_stage(const float* a, int as, const float4* 
   }
 }
 
-// Row tile of this workgroup.  Workgroups go to the 8 XCDs round robin by dispatch id, so in plain
-// order a tile's neighbours -- whose rows are its conv halo (dilation < FR) or its shifted taps -- sit
-// on other XCDs and every tile fetches its halo / taps through its own L2 again.  xcd_runs: XCD x gets
-// a contiguous run of tiles; row_perm p > 1 (taps shift by p whole tiles): the runs walk the tiles
-// 0, p, 2p, ..., 1, 1 + p, ... so a tile and its shifted taps share the run (the GEMM's block_tile
-// does the same for the dilated-conv GEMMs).
-__device__ __forceinline__ int frl_tile(const FrlArgs& g) {
-  const int id = blockIdx.x;
-  if (!g.xcd_runs) return id;
-  const int nt = gridDim.x, q = nt / 8, rr = nt % 8, x8 = id % 8, i8 = id / 8;
-  int t = (x8 < rr ? x8 * (q + 1) : rr * (q + 1) + (x8 - rr) * q) + i8;
-  if (g.row_perm > 1) {
-    const int per = nt / g.row_perm;
-    t = (t % per) * g.row_perm + t / per;
-  }
-  return t;
-}
+// row tile of this workgroup (frl_dev.h)
+__device__ __forceinline__ int frl_tile(const FrlArgs& g) { return frl_tile_id(g.xcd_runs, g.row_perm); }
 
 // PAIR: the activation ring holds stage PAIRS -- threads 0..255 stage the even stage of a pair, 256..511
 // the odd one, and the workgroup synchronises once per 64 k instead of once per 32 k; the 1x1 phase reads
@@ -358,11 +310,13 @@ __global__ __launch_bounds__(FT) void frl_kernel(FrlArgs g) {
 // dst[((st * 8 + w) * 4 + q) * 64 + lane] = float4(src[n = 32 w + lane % 32][32 st + 16 (lane / 32) + 4 q ..])
 // Up to FRAG_JOBS matrices per launch, each with its own K and leading dim (a layer stack's conv and 1x1
 // weights, forward and backward orientations, in one launch); blocks past a matrix's K stages exit.
+// A transposing job reads the matrix as [K][FN] (src[k * ld + n]): the fused MS-TCN++ backward's W_fu^T halves.
 struct PackFragArgs {
   const float* src[FRAG_JOBS];
   float* dst[FRAG_JOBS];
   int ld[FRAG_JOBS];
   int K[FRAG_JOBS];
+  unsigned long long trans;   // bit m: job m transposes
 };
 
 __global__ __launch_bounds__(256) void pack_frag_kernel(PackFragArgs a) {
@@ -370,7 +324,13 @@ __global__ __launch_bounds__(256) void pack_frag_kernel(PackFragArgs a) {
   if (st * FBK >= a.K[m]) return;
   const int q = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int n = w * 32 + (lane & 31), k = st * FBK + 16 * (lane >> 5) + 4 * q;
-  const float4 v = ld4(a.src[m] + (long long)n * a.ld[m] + k);
+  float4 v;
+  if ((a.trans >> m) & 1ull) {   // (a wave's 32 n are contiguous in every one of the 4 rows it reads)
+    const float* c = a.src[m] + (long long)k * a.ld[m] + n;
+    v = make_float4(c[0], c[a.ld[m]], c[2ll * a.ld[m]], c[3ll * a.ld[m]]);
+  } else {
+    v = ld4(a.src[m] + (long long)n * a.ld[m] + k);
+  }
   st4(a.dst[m] + ((long long)((st * 8 + w) * 4 + q) * 64 + lane) * 4, v);
 }
 
@@ -382,7 +342,7 @@ extern "C" int fx_debug_frl_stamps(unsigned long long* out) {
 }
 #endif
 
-bool frl_fills_device(long long rows) {
+bool frl_fills_device(long long rows, int min_fill_pct) {
   static std::mutex mu;
   static std::map<int, int> cus;
   int dev = 0;
@@ -398,7 +358,7 @@ bool frl_fills_device(long long rows) {
       n = it->second;
     }
   }
-  return (rows + FR - 1) / FR >= (long long)n * knobs().frl_min_fill / 100;
+  return (rows + FR - 1) / FR >= (long long)n * (min_fill_pct >= 0 ? min_fill_pct : knobs().frl_min_fill) / 100;
 }
 
 bool frl_supported(int F, const void* x, long long ldx, long long ld_other) {
@@ -412,11 +372,13 @@ int launch_pack_frag(const FragJob* jobs, int n, hipStream_t s) {
   PackFragArgs a{};
   int kmax = 0;
   for (int i = 0; i < n; ++i) {
-    FX_REQUIRE(jobs[i].K % FBK == 0 && jobs[i].ld % 4 == 0 && jobs[i].ld >= jobs[i].K, "pack_frag: K % 32 == 0");
+    FX_REQUIRE(jobs[i].K % FBK == 0 && jobs[i].ld % 4 == 0 && jobs[i].ld >= (jobs[i].trans ? FN : jobs[i].K),
+               "pack_frag: K % 32 == 0");
     a.src[i] = jobs[i].src;
     a.dst[i] = jobs[i].dst;
     a.ld[i] = jobs[i].ld;
     a.K[i] = jobs[i].K;
+    if (jobs[i].trans) a.trans |= 1ull << i;
     kmax = std::max(kmax, jobs[i].K);
   }
   fx_launch(pack_frag_kernel, dim3(kmax / FBK, FN / 32, n), dim3(256), 0, s, a);

@@ -226,13 +226,16 @@ bool frl_supported(int F, const void* x, long long ldx, long long ld_other);
 // whether rows / 32 row tiles cover FX_FRL_MIN_FILL (80) % of the CUs of the current device: below that the
 // fused layer leaves too many CUs idle and the two tuned GEMMs are faster (T = 2048 x 2 videos, 50 %: 11.6-11.8
 // vs 12.0 ms per step; the shipped yaml's 4096 + 2900 rows, 86 %: the fused layer 0.5 ms faster)
-bool frl_fills_device(long long rows);
+// (min_fill_pct >= 0: that percentage instead of FX_FRL_MIN_FILL -- the MS-TCN++ layer's FX_FRL2_MIN_FILL)
+bool frl_fills_device(long long rows, int min_fill_pct = -1);
 long long frl_packed_floats(int K);
 // one matrix [FN][K] (leading dim ld) -> fragment order at dst (frl_packed_floats(K) floats)
+// (trans: the source is [K][FN], src[k * ld + n] -- the packed image is that of its transpose)
 struct FragJob {
   const float* src;
   float* dst;
   int ld, K;
+  int trans = 0;
 };
 constexpr int FRAG_JOBS = 48;   // matrices per pack launch
 int launch_pack_frag(const FragJob* jobs, int n, hipStream_t s);
@@ -242,6 +245,27 @@ int launch_frl(const float* x, long long ldx, int M, int T, int dil, int dir, co
                const float* gate2, long long ldg2, float* out2, long long ldo2, float drop_p,
                unsigned long long drop_seed, hipStream_t s, float vdrop_p = 0.f, unsigned long long vdrop_seed = 0,
                float* out3 = nullptr, long long ldo3 = 0);
+
+// fused MS-TCN++ layer step (mstcn2_fused.hip, per call: fx_mstcn2_params.fused_layers), F = 256 rows as
+// launch_frl's; every weight matrix in the packed fragment order of launch_pack_frag
+struct Frl2Layer {
+  int M, T;                       // rows; uniform videos of T rows (seq_off NULL)
+  int dil1, dil2;                 // dilations of conv_d1 / conv_d2
+  const int* seq_off;             // ragged videos: host (nseq + 1) row offsets, <= 16 videos
+  int nseq;
+  float drop_p;                   // fwd: layer i's dropout on r_i; bwd: layer i - 1's, on G_i as dU_i-1 reads it
+  unsigned long long drop_seed;   // fx_drop_subseed(seed, that layer)
+};
+// cat = [conv_d1(f) + b1 | conv_d2(f) + b2] (ld 2F), r = dropout(relu(cat . W_fu^T + bfu)), fnext = f + r;
+// w1p / w2p: the forward conv images (K = 3F), wfup: W_fu (K = 2F)
+int launch_frl2_fwd(const Frl2Layer& y, const float* f, const float* w1p, const float* w2p, const float* b1,
+                    const float* b2, float* cat, const float* wfup, const float* bfu, float* r, float* fnext,
+                    hipStream_t s);
+// gout = gnext + conv_d1^T(dcat[:, 0:F]) + conv_d2^T(dcat[:, F:2F]), du = dropout(gout) * (rprev > 0),
+// dcat_prev = du . W_fu (ld 2F);  wb1p / wb2p: the dX conv images (K = 3F), wfutp: the two halves of W_fu^T
+// (K = F each, half h at h F F)
+int launch_frl2_bwd(const Frl2Layer& y, const float* dcat, const float* wb1p, const float* wb2p, const float* gnext,
+                    float* gout, const float* rprev, float* du, const float* wfutp, float* dcat_prev, hipStream_t s);
 
 // ---- grouped dilated Conv1d(k = 3) (conv_grouped.hip): nn.Conv1d(F, F, 3, groups = ngroup), cg = F / ngroup ----
 // Videos: nvid of T rows (rows = T * nvid) or the ragged host row offsets seq_off (nvid + 1, <= 16 videos);

@@ -31,10 +31,11 @@ struct ProfState {
   int kdropped = 0;            // kernels launched in a bracket after the pool ran out (not timed)
   hipStream_t open_stream = nullptr;
 };
-constexpr int kProfKinds = 15;  // 0 conv GEMM, 1 / 2 attention over T fwd / bwd, 3-6 X2Y cores of frame-level
+constexpr int kProfKinds = 16;  // 0 conv GEMM, 1 / 2 attention over T fwd / bwd, 3-6 X2Y cores of frame-level
                                 // calls (a2f fwd, a2f bwd, f2a fwd, f2a bwd), 7 fused MS-TCN layer, 8 persistent
                                 // token-kernel launches (tokdec.hip), 9 SCA frame-memory K/V projection GEMM,
-                                // 10 X2Y input projections (k, v, q), 11-14 X2Y cores of segment-level calls
+                                // 10 X2Y input projections (k, v, q), 11-14 X2Y cores of segment-level calls,
+                                // 15 fused MS-TCN++ layer
 std::mutex g_prof_mu;
 ProfState g_prof[kProfKinds];
 std::atomic<int> g_spin_override[2] = {{-1}, {-1}};   // fx_debug_set_spin: 0 token kernel, 1 X2Y f2a backward
@@ -136,6 +137,7 @@ const Knobs& knobs() {
     if (const char* p = env("FX_FRL_XCD")) k.frl_xcd = std::atoi(p);
     if (const char* p = env("FX_FRL_PAIR")) k.frl_pair = p[0] != '0';
     if (const char* p = env("FX_FRL_MIN_FILL")) k.frl_min_fill = std::atoi(p);
+    if (const char* p = env("FX_FRL2_MIN_FILL")) k.frl2_min_fill = std::atoi(p);
     if (const char* p = env("FX_AUX_STREAM")) k.aux_stream = p[0] != '0';
     if (const char* p = env("FX_GRU_POLL2")) k.gru_poll2 = p[0] != '0';
     if (const char* p = env("FX_GRU_STORE_WAVE")) k.gru_store_wave = std::max(0, std::min(2, std::atoi(p)));
@@ -293,7 +295,7 @@ int fx_prof_enable(int kind, int max_events) {
   // kernel-time pairs for the attention-over-T and X2Y kinds (a few kernels per call); the MFMA-bound kinds
   // (conv GEMM, fused layer chains, projection GEMMs) are timed by their brackets alone: their kernels run
   // back to back inside one C call, and an event pair per kernel would add its own dispatch gap to the chain
-  const bool kpairs = (kind >= 1 && kind <= 6) || kind >= 11;
+  const bool kpairs = (kind >= 1 && kind <= 6) || (kind >= 11 && kind <= 14);
   p.kev.resize(kpairs ? 2 * (size_t)max_events * 4 : 0);
   for (auto& e : p.kev) FX_CHECK_HIP(hipEventCreate(&e));
   p.flops.assign(max_events, 0.0);

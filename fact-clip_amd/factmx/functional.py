@@ -1310,6 +1310,13 @@ def mstcn(mod, x, T, nvid=1, seq_off=None):
     return MSTCNFn.apply(x2, meta, *params)
 
 
+# fx_mstcn2_params.fused_layers: the one-kernel MS-TCN++ layer (mstcn2_fused.hip; F = 256, dense convs, fp32
+# stream): 0 the GEMM launches per layer, 1 the fused layer where it applies and its row tiles cover
+# FX_FRL2_MIN_FILL (55) % of the CUs (819 vs 1080 us per 10-layer stack forward at 8192 rows),
+# 2 wherever it applies (tests, tools/m2_layer_bench.py).  Read at every forward and backward call.
+MSTCN2_FUSED_LAYERS = int(os.environ.get("FX_MSTCN2_FUSED_LAYERS", "1"))
+
+
 class MSTCN2Fn(torch.autograd.Function):
     """Whole ``MSTCN2.forward`` (basic.py:263-281, MS-TCN++) in one C call: per layer the two dilated
     convs store into the halves of one concat buffer, the 1x1 fusion GEMM applies bias + ReLU (+ the
@@ -1336,6 +1343,7 @@ class MSTCN2Fn(torch.autograd.Function):
         if not grads:
             prm.cin, prm.F, prm.cout, prm.num_layers, prm.in_map, prm.dil_factor = cin, F, cout, nl, int(in_map), dfac
             prm.ngroup = int(ngroup)     # grouped dilated convs (f_ngp); 1: dense
+            prm.fused_layers = int(MSTCN2_FUSED_LAYERS)
             prm.dropout, prm.seed = float(drop_p), int(seed)
             if seq_off is not None:
                 so = nx.int_array(seq_off)
@@ -1377,6 +1385,7 @@ class MSTCN2Fn(torch.autograd.Function):
         keep = []
         g = MSTCN2Fn._prm(ctx.meta, [t[0] for t in tg], keep, nx.Mstcn2Grads, grads=True)
         dx = _empty(*x.shape, device=dev) if ctx.needs_input_grad[0] else None
+        ctx.prm.fused_layers = int(MSTCN2_FUSED_LAYERS)   # (the backward decides for itself, whatever the forward ran)
         ws = _ws(lib.fx_mstcn2_workspace_floats(ctypes.byref(ctx.prm), x.shape[0]), dev)
         defer = _may_defer(tg)
         ctx.prm.side_defer = int(defer)

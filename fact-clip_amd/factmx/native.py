@@ -12,7 +12,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FACTMX_LIB", os.path.join(_HERE, "_lib", "libfactmx.so"))
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 P = ctypes.c_void_p
 I = ctypes.c_int
@@ -53,7 +53,7 @@ class Mstcn2Params(ctypes.Structure):
     _fields_ = [("cin", I), ("F", I), ("cout", I), ("num_layers", I), ("in_map", I), ("dil_factor", I),
                 ("w_in", P), ("b_in", P), ("w_d1", P), ("b_d1", P), ("w_d2", P), ("b_d2", P), ("w_fu", P),
                 ("b_fu", P), ("w_out", P), ("b_out", P), ("dropout", F), ("seed", U), ("side_defer", I),
-                ("seq_off", P), ("ngroup", I)]
+                ("seq_off", P), ("ngroup", I), ("fused_layers", I)]
 
 
 class Mstcn2Grads(ctypes.Structure):
@@ -90,6 +90,7 @@ STATUS_X2Y_TIMEOUT = 4   # FX_STATUS_X2Y_TIMEOUT: the one-launch X2Y f2a backwar
 LOSS_MAXK = 512        # FX_LOSS_MAXK: matched columns of an attention loss term
 LOSS_NB = 128          # FX_LOSS_NB: row blocks per loss term
 TERM_CLASS, TERM_ATTN, TERM_INFONCE, TERM_VNCLASS = 0, 1, 2, 3
+PROF_MSTCN2_FUSED = 15   # fx_prof kind of the fused MS-TCN++ layer chains (11-14: segment-level X2Y cores)
 PREC_DEFAULT, PREC_F32, PREC_BF16, PREC_F32S, PREC_F32S2 = -1, 0, 1, 2, 3   # FX_PREC_*: GEMM arithmetic
 
 

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define FX_ABI_VERSION 28
+#define FX_ABI_VERSION 29
 
 enum {
   FX_OK = 0,
@@ -378,6 +378,14 @@ typedef struct fx_mstcn2_params {
   const int* seq_off;         /* ragged videos, as fx_mstcn_params.seq_off */
   int ngroup;                 /* groups of both dilated convs of every layer, as fx_mstcn_params.ngroup
                                  (0 and 1: dense); the fusion 1x1 stays dense */
+  int fused_layers;           /* the fused one-kernel MS-TCN++ layer (both dilated convs -> fusion 1x1 ->
+                                 ReLU, dropout, residual forward; the input-gradient chain backward):
+                                 0 off; 1 where it applies (F = 256, dense convs, <= 16 ragged or uniform
+                                 videos, the stream in FX_PREC_F32) and its 32-row tiles cover
+                                 FX_FRL2_MIN_FILL (default 55) % of the CUs; 2 wherever it applies (tests).
+                                 fwd and bwd each decide for themselves: the backward packs its own
+                                 weights, so the value (or the stream's precision) may differ between
+                                 the two calls.  Everything else keeps the GEMM launches */
 } fx_mstcn2_params;
 
 typedef struct fx_mstcn2_grads {
@@ -992,7 +1000,9 @@ int fx_get_default_precision(void);
  *   8 = persistent token-kernel launches of the decoders (tokdec.hip programs),
  *   9 = SCA frame-memory K/V projection GEMM (every layer's keys and values in one
  *       frame-level product, M = frames, N = 2 d_model layers, K = memory width),
- *   10 = X2Y input projections (k, v from X, q from Y: three products per call).
+ *   10 = X2Y input projections (k, v from X, q from Y: three products per call),
+ *   15 = fused MS-TCN++ layer (frl2_kernel: the forward chain of a stack, or its fused
+ *        input-gradient chain; one bracket per chain with its launch count).
  * fx_prof_enable resets one kind; fx_prof_disable resets all.
  * fx_prof_collect: the event brackets around each call (its kernels plus any host-issue gap
  *   between them).  fx_prof_collect_kernels: the same calls' kernels alone -- every kernel
