@@ -435,6 +435,7 @@ int launch_gru_fwd(const float* gi, long long ldgi, int nseq, const int* seq_off
                    const float* const bhh[2], float* out, long long ldo, int relu_out, float* saved, float* ws,
                    unsigned* status, int spin_max, hipStream_t s) {
   FX_REQUIRE(Hh > 0 && Hh <= NW * MAXU, "gru: hidden size per direction must be <= 256");
+  FX_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 7) == 0, "gru: the sync area must be 8-byte aligned");
   const int Stot = seq_off[nseq];
   if (Stot == 0) return FX_OK;
   unsigned* tmo = reinterpret_cast<unsigned*>(ws);
@@ -473,6 +474,7 @@ int launch_gru_bwd(const float* dout, long long lddo, const float* relu_y, long 
                    int Hh, const float* const whh[2], const float* saved, float* dgi, long long lddgi, float* dgh,
                    float* sync_ws, unsigned* status, int spin_max, hipStream_t s) {
   FX_REQUIRE(Hh > 0 && Hh <= NW * MAXU, "gru: hidden size per direction must be <= 256");
+  FX_REQUIRE((reinterpret_cast<uintptr_t>(sync_ws) & 7) == 0, "gru: the sync area must be 8-byte aligned");
   const int Stot = seq_off[nseq];
   if (Stot == 0) return FX_OK;
   const int H3 = 3 * Hh;

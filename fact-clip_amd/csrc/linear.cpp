@@ -318,12 +318,20 @@ static long long gru_split_ws(int S, int In, int Hh) {
   return std::max(sp, split_ws(S, In, 3 * Hh));
 }
 
-// fwd: [sync area][gi (S, 6Hh)];  bwd: [dgi (S, 6Hh)][dgh 2 x (S, 3Hh)][split-K][colsum][sync area]
+// Offset of the backward's sync area, rounded up to an even number of floats: its granules are 8-byte atomics,
+// and with an odd Hh the tables before it hold an odd number of floats (a granule straddling two 4-byte words
+// is stored and polled in halves, so a reader can pair the new epoch with the previous step's value)
+static long long gru_bwd_sync_off(int S, int In, int Hh) {
+  const long long H3 = 3LL * Hh;
+  const long long n = S * 2 * H3 + 2 * S * H3 + gru_split_ws(S, In, Hh) + colsum_workspace_floats(S, 3 * Hh);
+  return (n + 1) & ~1LL;
+}
+
+// fwd: [sync area][gi (S, 6Hh)];  bwd: [dgi (S, 6Hh)][dgh 2 x (S, 3Hh)][split-K][colsum][pad to 8 B][sync area]
 long long fx_gru_workspace_floats(int S, int nseq, int In, int Hh) {
   const long long H3 = 3LL * Hh;
   long long fwd = gru_sync_floats(Hh, nseq) + S * 2 * H3;
-  long long sp = gru_split_ws(S, In, Hh);
-  long long bwd = S * 2 * H3 + 2 * S * H3 + sp + colsum_workspace_floats(S, 3 * Hh) + gru_sync_floats(Hh, nseq);
+  long long bwd = gru_bwd_sync_off(S, In, Hh) + gru_sync_floats(Hh, nseq);
   return std::max(fwd, bwd);
 }
 
@@ -368,7 +376,7 @@ int fx_gru_bidir_bwd(const float* x, long long ldx, int S, int nseq, const int* 
   float* spl = dgh + 2LL * S * H3;
   float* csw = spl + gru_split_ws(S, In, Hh);
   WsBound wb(spl, gru_split_ws(S, In, Hh));
-  float* sync_ws = csw + colsum_workspace_floats(S, 3 * Hh);
+  float* sync_ws = workspace + gru_bwd_sync_off(S, In, Hh);
   const float* whh[2] = {w_hh_f, w_hh_r};
   FX_TRY(launch_gru_bwd(dout, lddo, relu_y, ldy, nq, off.data(), Hh, whh, saved, dgi, 2 * H3, dgh, sync_ws,
                         (unsigned*)status, spin_max, s));

@@ -734,6 +734,8 @@ int fx_seg_sum_rows(const float* dx, long long lddx, const int32_t* seg_start, c
  *   (status: caller-owned device int32, nullable, never cleared by the library).  The
  *   outputs are then wrong: the caller reads the word at its next host read-back and
  *   fails (factmx raises FactmxNativeError).
+ * workspace (fx_gru_workspace_floats): 8-byte aligned -- the exchange uses 8-byte atomics -- or the
+ *   call is refused.
  * ---------------------------------------------------------------------- */
 #define FX_STATUS_GRU_TIMEOUT 1
 #define FX_STATUS_TOK_TIMEOUT 2   /* fx_decoder_*: a persistent token-kernel barrier wait gave up */
