@@ -234,6 +234,37 @@ int launch_gemm_group(const fx_gemm_desc* d, int n, hipStream_t s) {
 
 extern "C" {
 
+// The plan of desc as launch_gemm would make it on a stream of precision prec (host only)
+int fx_gemm_plan(const fx_gemm_desc* desc, int prec, fx_gemm_plan_info* out) {
+  FX_REQUIRE(desc && out, "fx_gemm_plan: null argument");
+  FX_REQUIRE(fx::valid_precision(prec), "fx_gemm_plan: FX_PREC_F32, FX_PREC_BF16, FX_PREC_F32S or FX_PREC_F32S2");
+  *out = fx_gemm_plan_info{};
+  const fx_gemm_desc& d = *desc;
+  FX_REQUIRE(d.M >= 0 && d.N >= 0 && d.K >= 0 && d.batch >= 1, "gemm: bad sizes");
+  if (d.M == 0 || d.N == 0) return FX_OK;
+  fx::GemmPlan P;
+  FX_TRY(fx::plan_gemm(d, prec, fx::knobs(), 0, P));
+  out->family = P.family;
+  out->a_kind = P.ak;
+  out->b_kind = P.bk;
+  out->fast = P.fast ? 1 : 0;
+  out->np = P.np;
+  out->split = P.g.split;
+  out->kt_per_split = P.g.kt_per_split;
+  out->tiles_x = P.g.tiles_x;
+  out->tiles_y = P.g.tiles_y;
+  out->grid_x = (int)P.grid.x;
+  out->grid_y = (int)P.grid.y;
+  out->grid_z = (int)P.grid.z;
+  out->block = (int)P.block.x;
+  out->in_launch_reduce = P.counters > 0 ? 1 : 0;
+  out->xcd_planes = P.g.xcd_planes;
+  out->row_perm = P.g.row_perm;
+  out->group_m = P.g.group_m;
+  out->persist = P.g.persist;
+  return FX_OK;
+}
+
 int fx_set_stream_precision(void* stream, int prec) {
   FX_REQUIRE(prec == FX_PREC_DEFAULT || fx::valid_precision(prec),
              "gemm precision: FX_PREC_DEFAULT, FX_PREC_F32, FX_PREC_BF16, FX_PREC_F32S or FX_PREC_F32S2");

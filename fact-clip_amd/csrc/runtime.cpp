@@ -269,6 +269,7 @@ long long fx_struct_size(int which) {
     case 5: return (long long)sizeof(fx_mstcn2_params);
     case 6: return (long long)sizeof(fx_vn_term);
     case 7: return (long long)sizeof(fx_vn_video);
+    case 8: return (long long)sizeof(fx_gemm_plan_info);
     default: return -1;
   }
 }

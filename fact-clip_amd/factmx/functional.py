@@ -1433,7 +1433,10 @@ def _rows_operand(t, trans=False):
 
 
 def gemm(M, N, K, a, b, c, ldc, bias=None, relu=0, resid=None, alpha=1.0, beta=0.0, gate=None, c_tap_cin=0,
-         split=1, c_last=None, batch=1, c_bs=0):
+         split=1, c_last=None, batch=1, c_bs=0, plan=None, ws=None):
+    """One fx_gemm launch.  plan: an nx.GemmPlanInfo, filled with fx_gemm_plan's answer for this very descriptor
+    at the current stream's precision before the launch.  ws: the split-K workspace (at least
+    fx_gemm_workspace_floats floats), allocated here when None."""
     lib = nx.load()
     d = nx.GemmDesc()
     d.M, d.N, d.K, d.batch = M, N, K, batch
@@ -1447,10 +1450,18 @@ def gemm(M, N, K, a, b, c, ldc, bias=None, relu=0, resid=None, alpha=1.0, beta=0
     d.relu, d.c_tap_cin = relu, c_tap_cin
     d.c_last_col = nx.ptr(c_last)
     d.split_k = split
-    ws = None
     if split > 1:
-        ws = _ws(lib.fx_gemm_workspace_floats(ctypes.byref(d)), c.device)
+        need = lib.fx_gemm_workspace_floats(ctypes.byref(d))
+        if ws is None:
+            ws = _ws(need, c.device)
+        elif ws.numel() < need or ws.dtype != torch.float32 or not ws.is_contiguous():
+            raise ValueError(f"gemm: the split-K workspace needs {need} contiguous fp32 elements")
         d.workspace = nx.ptr(ws)
+    else:
+        ws = None
+    if plan is not None:
+        _check(lib.fx_gemm_plan(ctypes.byref(d), lib.fx_get_stream_precision(nx.stream()), ctypes.byref(plan)),
+               "fx_gemm_plan")
     _check(lib.fx_gemm(ctypes.byref(d), nx.stream()), "fx_gemm")
     return ws
 

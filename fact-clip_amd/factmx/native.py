@@ -12,7 +12,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FACTMX_LIB", os.path.join(_HERE, "_lib", "libfactmx.so"))
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 P = ctypes.c_void_p
 I = ctypes.c_int
@@ -40,6 +40,13 @@ class GemmDesc(ctypes.Structure):
                 ("split_k", I), ("workspace", P), ("c_last_col", P), ("dbg_stamps", P), ("drop_p", F),
                 ("drop_seed", U), ("c_last_batch_stride", L), ("b_dil_growth", I),
                 ("a_dil_b1", I), ("bias_batch_stride", L)]
+
+
+class GemmPlanInfo(ctypes.Structure):
+    """fx_gemm_plan_info: what fx_gemm decides before it launches a descriptor (fx_gemm_plan, host only)."""
+    _fields_ = [(n, I) for n in ("family", "a_kind", "b_kind", "fast", "np", "split", "kt_per_split", "tiles_x",
+                                 "tiles_y", "grid_x", "grid_y", "grid_z", "block", "in_launch_reduce", "xcd_planes",
+                                 "row_perm", "group_m", "persist")]
 
 
 class MstcnParams(ctypes.Structure):
@@ -92,6 +99,9 @@ LOSS_NB = 128          # FX_LOSS_NB: row blocks per loss term
 TERM_CLASS, TERM_ATTN, TERM_INFONCE, TERM_VNCLASS = 0, 1, 2, 3
 PROF_MSTCN2_FUSED = 15   # fx_prof kind of the fused MS-TCN++ layer chains (11-14: segment-level X2Y cores)
 PREC_DEFAULT, PREC_F32, PREC_BF16, PREC_F32S, PREC_F32S2 = -1, 0, 1, 2, 3   # FX_PREC_*: GEMM arithmetic
+GEMM_FAM_TILED, GEMM_FAM_WIDE8, GEMM_FAM_BF16, GEMM_FAM_SPLIT, GEMM_FAM_DIRECT = range(5)   # FX_GEMM_FAM_*
+(GEMM_KIND_ROWS, GEMM_KIND_ROWS_CONV, GEMM_KIND_ROWS_GEN, GEMM_KIND_COLS, GEMM_KIND_COLS_CONV, GEMM_KIND_ROWS_CAT,
+ GEMM_KIND_COLS_CONVR, GEMM_KIND_COLS_KT) = range(8)   # FX_GEMM_KIND_*
 
 
 class LossTerm(ctypes.Structure):
@@ -121,7 +131,8 @@ class VnVideo(ctypes.Structure):
 
 
 # fx_struct_size ids
-ABI_STRUCTS = (GemmDesc, DecoderParams, MstcnParams, LossTerm, VideoAttn, Mstcn2Params, VnTerm, VnVideo)
+ABI_STRUCTS = (GemmDesc, DecoderParams, MstcnParams, LossTerm, VideoAttn, Mstcn2Params, VnTerm, VnVideo,
+               GemmPlanInfo)
 
 
 # name -> (restype, argtypes); every fx_* symbol declared in include/factmx.h
@@ -131,6 +142,7 @@ SIGNATURES = {
     "fx_struct_size": (L, [I]),
     "fx_gemm": (I, [ctypes.POINTER(GemmDesc), P]),
     "fx_gemm_workspace_floats": (L, [ctypes.POINTER(GemmDesc)]),
+    "fx_gemm_plan": (I, [ctypes.POINTER(GemmDesc), I, ctypes.POINTER(GemmPlanInfo)]),
     "fx_linear_fwd": (I, [P, L, P, L, I, I, I, P, L, P, P, L, I, I, P]),
     "fx_linear_bwd_workspace_floats": (L, [I, I, I]),
     "fx_linear_bwd": (I, [P, L, P, L, P, L, P, L, I, I, I, P, L, P, L, P, I, I, P, P]),

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define FX_ABI_VERSION 29
+#define FX_ABI_VERSION 30
 
 enum {
   FX_OK = 0,
@@ -39,7 +39,7 @@ enum {
 int fx_version(void);
 const char* fx_last_error(void);
 /* sizeof of the ABI structs (0 gemm_desc, 1 decoder_params, 2 mstcn_params, 3 loss_term,
- * 4 video_attn, 5 mstcn2_params, 6 vn_term, 7 vn_video) so bindings can check their layouts; -1 for an unknown id */
+ * 4 video_attn, 5 mstcn2_params, 6 vn_term, 7 vn_video, 8 gemm_plan_info) so bindings can check their layouts; -1 for an unknown id */
 long long fx_struct_size(int which);
 
 /* ------------------------------------------------------------------------
@@ -120,6 +120,46 @@ typedef struct fx_gemm_desc {
 
 int fx_gemm(const fx_gemm_desc* desc, void* stream);
 long long fx_gemm_workspace_floats(const fx_gemm_desc* desc);
+
+/* What fx_gemm decides before it launches `desc` on a stream of GEMM precision `prec` (FX_PREC_F32, FX_PREC_BF16,
+ * FX_PREC_F32S or FX_PREC_F32S2): the kernel family, the operand kinds, the split, the tiles, the grid and the
+ * tile order.  Host only: no HIP call, no stream, no allocation.  The planner never dereferences the device
+ * pointers of the descriptor (operands, c, workspace, epilogue inputs): it tests them for NULL and for 16-byte
+ * alignment only, so a caller without a GPU may pass made-up addresses.  (seq_off is a HOST array and is read.)
+ * Returns what the planner returns (FX_ERR_UNSUPPORTED for operand kinds no kernel runs, FX_ERR_SHAPE for a
+ * descriptor fx_gemm refuses); FX_OK with a zeroed *out for M == 0 or N == 0, where fx_gemm launches nothing. */
+enum { FX_GEMM_FAM_TILED = 0, FX_GEMM_FAM_WIDE8 = 1, FX_GEMM_FAM_BF16 = 2, FX_GEMM_FAM_SPLIT = 3, FX_GEMM_FAM_DIRECT = 4 };
+enum {
+  FX_GEMM_KIND_ROWS = 0,
+  FX_GEMM_KIND_ROWS_CONV = 1,
+  FX_GEMM_KIND_ROWS_GEN = 2,
+  FX_GEMM_KIND_COLS = 3,
+  FX_GEMM_KIND_COLS_CONV = 4,
+  FX_GEMM_KIND_ROWS_CAT = 5,
+  FX_GEMM_KIND_COLS_CONVR = 6,
+  FX_GEMM_KIND_COLS_KT = 7
+};
+typedef struct fx_gemm_plan_info {
+  int family;                 /* FX_GEMM_FAM_* */
+  int a_kind;                 /* FX_GEMM_KIND_* of each operand */
+  int b_kind;
+  int fast;                   /* FAM_TILED: the vector loaders (0: the generic element fetch) */
+  int np;                     /* FAM_WIDE8 / FAM_SPLIT: bf16 pieces per fp32 operand (0: f32 MFMA) */
+  int split;                  /* K slices actually taken (<= split_k) */
+  int kt_per_split;           /* k steps per slice: 64-deep stages, 32-deep chunks on FAM_DIRECT */
+  int tiles_x;                /* output tiles: 64 columns by 64 or (wide families) 128 rows; 32 x 32 on FAM_DIRECT */
+  int tiles_y;
+  int grid_x;
+  int grid_y;
+  int grid_z;
+  int block;                  /* threads per workgroup */
+  int in_launch_reduce;       /* split > 1: the last workgroup of a tile reduces (0: a separate reduce launch) */
+  int xcd_planes;             /* tile order: whole z-planes per XCD */
+  int row_perm;               /* > 1: row tiles permuted by this stride (dilated-conv A) */
+  int group_m;                /* > 1: tiles in groups of this many row tiles */
+  int persist;                /* > 0: tiles walked by a persistent grid of grid_x workgroups */
+} fx_gemm_plan_info;
+int fx_gemm_plan(const fx_gemm_desc* desc, int prec, fx_gemm_plan_info* out);
 
 /* ------------------------------------------------------------------------
  * nn.Linear / Conv1d(k=1) on (M, K) rows.  Replaces basic.py:139,177,182,

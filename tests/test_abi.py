@@ -55,7 +55,8 @@ def test_struct_layouts():
     # fx_operand / fx_gemm_desc field lists mirror the header order (sizes are what the C side reads)
     src = open(HEADER).read()
     for struct, cls in (("fx_operand", nx.Operand), ("fx_gemm_desc", nx.GemmDesc),
-                        ("fx_mstcn_params", nx.MstcnParams), ("fx_mstcn_grads", nx.MstcnGrads)):
+                        ("fx_mstcn_params", nx.MstcnParams), ("fx_mstcn_grads", nx.MstcnGrads),
+                        ("fx_gemm_plan_info", nx.GemmPlanInfo)):
         body = re.search(r"typedef struct\s+" + struct + r"\s*\{(.*?)\}\s*" + struct + r"\s*;", src, flags=re.S).group(1)
         body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
         body = re.sub(r"//[^\n]*", "", body)

@@ -1,12 +1,14 @@
-"""fx_gemm across both kernels (64x64 LDS-tiled / direct small-shape) and every epilogue option,
+"""fx_gemm across its kernels (64x64 LDS-tiled / 128x64 wide / direct small-shape) and every epilogue option,
 vs float64 torch on the same inputs (GPU).  Shapes are picked so the automatic path choice
 exercises: direct (token rows, shallow K, few tiles, batched heads, cross-block split-K with the
-fused last-block reduction) and tiled (with and without split-K)."""
+fused last-block reduction) and tiled (with and without split-K, reduced in the launch and by the
+reduce launch); every case asserts the path it names through the plan query fx_gemm_plan."""
 import pytest
 import torch
 
 from factmx import functional as fxf
 from factmx import native as nx
+from gemm_cases import im2col
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -27,28 +29,34 @@ def _operand(t2d_or_3d, trans, batch_stride=0):
     return o
 
 
+D, T, W = nx.GEMM_FAM_DIRECT, nx.GEMM_FAM_TILED, nx.GEMM_FAM_WIDE8
 CASES = [
-    # M, N, K, batch, a_trans, b_trans, split
-    (32, 512, 512, 1, False, False, 1),     # token projection (direct)
-    (32, 256, 1024, 1, False, True, 4),     # token dX (direct, split-K)
-    (256, 257, 32, 1, True, True, 1),       # token dW, K = Nact (direct)
-    (256, 257, 4096, 1, True, True, 13),    # frame-level dW, few tiles (direct, split-K)
-    (4096, 32, 32, 8, True, True, 1),       # per-head attention products (direct, batched)
-    (32, 32, 4096, 8, False, True, 32),     # per-head dK/dV-like (direct, batched split-K)
-    (96, 200, 1000, 1, False, False, 1),    # ragged edges (direct)
-    (7, 5, 3, 1, False, True, 1),           # tiny
-    (600, 520, 300, 1, False, False, 1),    # tiled
-    (600, 520, 3000, 1, True, False, 6),    # tiled split-K, fused reduction
-    (1000, 700, 77, 2, False, True, 1),     # tiled, batched, ragged
-    (600, 520, 3001, 1, True, True, 6),     # weight gradient, K tail (COLS_KT: rows past K read as zero)
-    (512, 513, 6996, 1, True, True, 13),    # the shipped yaml's ragged 4096 + 2900 rows (K tail, wide tile)
-    (640, 256, 1000, 2, True, True, 1),     # K tail, batched
+    # M, N, K, batch, a_trans, b_trans, split, the plan the label claims: (family, split taken, in-launch reduction),
+    # asserted through fx_gemm_plan on the launched descriptor
+    (32, 512, 512, 1, False, False, 1, (D, 1, 0)),      # token projection (direct)
+    (32, 256, 1024, 1, False, True, 4, (D, 4, 1)),      # token dX (direct, split-K, last block reduces)
+    (256, 257, 32, 1, True, True, 1, (D, 1, 0)),        # token dW, K = Nact (direct)
+    (256, 257, 4096, 1, True, True, 13, (T, 13, 0)),    # frame-level dW, few tiles: K > 2048 keeps it tiled, reduce launch
+    (4096, 32, 32, 8, True, True, 1, (D, 1, 0)),        # per-head attention products (direct, batched)
+    (32, 32, 4096, 8, False, True, 32, (D, 16, 0)),     # per-head dK/dV-like (direct, batched, split 16: reduce launch)
+    (96, 200, 1000, 1, False, False, 1, (D, 1, 0)),     # ragged edges (direct)
+    (7, 5, 3, 1, False, True, 1, (D, 1, 0)),            # tiny
+    (600, 520, 300, 1, False, False, 1, (D, 1, 0)),     # K <= 512 with a K tail: direct
+    (800, 700, 320, 1, False, False, 1, (T, 1, 0)),     # tiled, FAST loaders
+    (600, 520, 3000, 1, True, False, 6, (T, 6, 0)),     # tiled split-K, 6 slabs: reduce launch
+    (600, 520, 3000, 1, True, False, 2, (T, 2, 1)),     # tiled split-K, 2 slabs: the last block of a tile reduces
+    (1000, 700, 77, 2, False, True, 1, (D, 1, 0)),      # batched, ragged, shallow K tail: direct
+    (1000, 700, 577, 2, False, True, 1, (T, 1, 0)),     # tiled, batched, ragged (K tail on the generic loop)
+    (600, 520, 3001, 1, True, True, 6, (W, 6, 0)),      # weight gradient, K tail (COLS_KT: rows past K read as zero), wide tile
+    (600, 520, 3001, 1, True, True, 3, (T, 3, 0)),      # the same on the 64 x 64 kernel's K-tail loaders
+    (512, 513, 6996, 1, True, True, 13, (T, 13, 0)),    # the shipped yaml's ragged 4096 + 2900 rows (ld 513: generic loop)
+    (640, 256, 1000, 2, True, True, 1, (D, 1, 0)),      # K tail, batched, few tiles: direct
 ]
 
 
-@pytest.mark.parametrize("M,N,K,batch,at,bt,split", CASES)
+@pytest.mark.parametrize("M,N,K,batch,at,bt,split,want", CASES, ids=["-".join(str(v) for v in c[:7]) for c in CASES])
 @pytest.mark.parametrize("epi", ["plain", "bias_relu_resid", "beta_gate"])
-def test_gemm(M, N, K, batch, at, bt, split, epi):
+def test_gemm(M, N, K, batch, at, bt, split, want, epi):
     A = _r(batch, M, K, seed=1)
     B = _r(batch, K, N, seed=2, scale=K ** -0.5)
     Ad = (A.transpose(1, 2) if at else A).contiguous().float().to(DEV)
@@ -69,8 +77,10 @@ def test_gemm(M, N, K, batch, at, bt, split, epi):
         ref = torch.where(gate > 0, ref + 0.5 * c0, torch.zeros_like(ref))
     elif epi != "plain":
         pytest.skip("epilogue operands are single-batch")
-    fxf.gemm(M, N, K, a, b, c, N, split=split, batch=batch, c_bs=M * N, **kw)
+    plan = nx.GemmPlanInfo()
+    fxf.gemm(M, N, K, a, b, c, N, split=split, batch=batch, c_bs=M * N, plan=plan, **kw)
     torch.cuda.synchronize()
+    assert (plan.family, plan.split, plan.in_launch_reduce) == want
     err = (c.double().cpu() - ref).abs().max().item()
     assert err <= 1e-5 * (1 + ref.abs().max().item()) + 1e-6 * K ** 0.5, err
 
@@ -103,20 +113,6 @@ def test_gemm_fused_bias_column(M, K, split):
 # the operand is not 16-B vector-loadable and the launch takes the generic loaders.
 def _f32(*shape, seed, scale=1.0):
     return _r(*shape, seed=seed, scale=scale).float().double()   # float64 holding exactly the fp32 inputs
-
-
-def _im2col(X, dil, seq_len):
-    """(R, cin) -> (R, 3 cin): column j cin + c of row r is X[r + (j - 1) dil, c], zero outside r's video."""
-    R, cin = X.shape
-    out = torch.zeros(R, 3 * cin, dtype=X.dtype)
-    for s in range(0, R, seq_len):
-        e = min(R, s + seq_len)
-        for j in range(3):
-            sh = (j - 1) * dil
-            lo, hi = max(s, s - sh), min(e, e - sh)
-            if hi > lo:
-                out[lo:hi, j * cin:(j + 1) * cin] = X[lo + sh:hi + sh]
-    return out
 
 
 def _dev(X, unaligned):
@@ -164,7 +160,7 @@ def _make_conv(R, cin, seq_len, dil, trans, u, seed):
     o = nx.Operand()
     o.ptr, o.ld, o.trans, o.conv_dir = nx.ptr(keep[0]), keep[0].shape[1], int(trans), 1
     o.conv_taps, o.conv_cin, o.conv_dil, o.seq_len = 3, cin, dil, seq_len
-    return o, _im2col(X, dil, seq_len), keep
+    return o, im2col(X, dil, seq_len), keep
 
 
 # shapes by family, from the planner's thresholds: wide8 from 192 tiles of 128 x 64 with K % 64 == 0; below that
@@ -212,9 +208,17 @@ def test_gemm_family_pairs(family, aform, bform, MN, prec):
         Bt = Bn.t()
     ref = A @ Bt
     c = torch.empty(M, N, device=DEV)
+    plan = nx.GemmPlanInfo()
     with fxf.gemm_precision(prec):
-        fxf.gemm(M, N, K, a, b, c, N)
+        fxf.gemm(M, N, K, a, b, c, N, plan=plan)
     torch.cuda.synchronize()
+    want = {"wide8": nx.GEMM_FAM_WIDE8, "tiled": nx.GEMM_FAM_TILED, "generic": nx.GEMM_FAM_TILED,
+            "direct": nx.GEMM_FAM_DIRECT}.get(family)
+    if family == "prec":   # the bf16 kernel; the split modes: the split kernel (B cols) / register split (B rows)
+        want = (nx.GEMM_FAM_BF16 if prec == "bf16" else
+                nx.GEMM_FAM_SPLIT if bform == "cols" else nx.GEMM_FAM_WIDE8)
+        assert plan.np == {"bf16": 0, "fp32s": 3, "fp32s2": 2}[prec]
+    assert plan.family == want and plan.fast == int(family == "tiled"), (plan.family, plan.fast)
     err = (c.double().cpu() - ref).abs()
     tol = 1e-5 * (1 + ref.abs().max().item()) + 1e-6 * K ** 0.5
     print(f"{family} {aform} x {bform} {prec}: max err {err.max().item():.3e} (fp32 tolerance {tol:.3e})")
