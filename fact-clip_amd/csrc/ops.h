@@ -88,7 +88,7 @@ int launch_gru_bwd(const float* dout, long long lddo, const float* relu_y, long 
                    int Hh, const float* const whh[2], const float* saved, float* dgi, long long lddgi, float* dgh,
                    float* sync_ws, unsigned* status, int spin_max, hipStream_t s);
 
-// X2Y attention cores (x2y_core.hip).  Token rows per video (keys of the a2f core, queries of the f2a core):
+// X2Y attention cores (x2y_a2f.hip, x2y_f2a.hip; shared device pieces: x2y_dev.h).  Token rows per video (keys of the a2f core, queries of the f2a core):
 // <= 64 take the original kernels, 65 .. FX_X2Y_MAXTOK their wide variants (the launchers choose by the call's
 // widest video); yoff / xoff: (nvid + 1) host row offsets, aoff: attention block offsets (ny_v * nx_v
 // row-major each)

@@ -6,7 +6,7 @@ the library usable (GPU).
   status word and check_device_status() raises; then, with the default bound back, more decoder calls than
   the kernel's 512 round-robin barrier slots (so the slot of the timed-out launch is dealt again) give
   outputs bitwise equal to the run before the timeout;
-* the one-launch X2Y f2a backward core (x2y_core.hip x2y_f2a_bwd_kernel<3>, the default for >= 64 key
+* the one-launch X2Y f2a backward core (x2y_f2a.hip x2y_f2a_bwd_kernel<3>, the default for >= 64 key
   chunks): the same with fx_debug_set_spin(1, 1) -> FX_STATUS_X2Y_TIMEOUT, then bitwise-equal gradients.
 The reference has no counterpart (its attention is torch.nn.MultiheadAttention, basic.py:396-523, 349-389):
 these are the failure paths of this library's own barriers."""

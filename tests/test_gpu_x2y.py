@@ -1,6 +1,6 @@
 """X2Y_map (basic.py:349-389) through X2YFn on the GPU against the fp64 oracle (fo.x2y), per video of a
 stacked ragged batch: the a2f direction (keys = action tokens: the fused one-launch core of
-x2y_core.hip for <= 64 keys, including two key blocks at 40 keys, and the grouped-GEMM path past 64
+x2y_a2f.hip for <= 64 keys, including two key blocks at 40 keys, and the grouped-GEMM path past 64
 keys), the f2a direction (keys = frames), and the core switched off (FX_X2Y_FUSED=0 equivalent: the
 grouped path) -- out, logit and attn forward, every input / weight gradient backward, with random
 upstream gradients on all three outputs.  The reference's losses read attn_logit only (blocks.py:372-377,
@@ -46,7 +46,12 @@ def _params(xdim, ydim, outdim, seed):
                                              ("f2a", 32, (700, 413)), ("f2a", 40, (300, 257, 65)),
                                              ("f2a", 64, (64, 1)), ("f2a", 75, (200, 90)),
                                              ("a2f", 32, (1,)), ("f2a", 7, (3000,)),
-                                             ("f2a", 32, (4096, 300))])
+                                             ("f2a", 32, (4096, 300)),
+                                             # edges of the shared phase bodies: the first key of the second
+                                             # key block, a second workgroup of one row, a one-row video;
+                                             # the first query of the second 32-row block, one key past a
+                                             # chunk, two chunks and a partial one
+                                             ("a2f", 33, (33, 1)), ("f2a", 33, (65, 130))])
 def test_x2y_vs_oracle(direction, nq, Ts):
     check_x2y(direction, nq, Ts)
 
@@ -84,7 +89,7 @@ def test_x2y_attn_not_differentiable_in_product():
 
 CASES = [("a2f", 32, (700, 413)), ("a2f", 40, (300, 257)), ("a2f", 64, (129, 64)), ("a2f", 75, (300, 200)),
          ("f2a", 32, (700, 413)), ("f2a", 40, (300, 257, 65)), ("f2a", 64, (64, 1)), ("f2a", 75, (200, 90)),
-         ("a2f", 32, (1,)), ("f2a", 7, (3000,))]
+         ("a2f", 32, (1,)), ("f2a", 7, (3000,)), ("a2f", 33, (33, 1)), ("f2a", 33, (65, 130))]
 
 
 def check_x2y(direction, nq, Ts):
@@ -153,6 +158,9 @@ def check_x2y(direction, nq, Ts):
     close(Yp.grad, torch.cat([t.grad for t in Ypr]), 1e-4, "dYpos")
     for n in P:
         close(W[n].grad, Pr[n].grad, 2e-4, n)
+    got = {"out": out, "logit": logit, "attn": attn, "dX": X.grad, "dY": Y.grad, "dXpos": Xp.grad, "dYpos": Yp.grad}
+    got.update({"d" + n: W[n].grad for n in P})
+    return got      # (for bitwise comparisons between two builds of the library)
 
 
 if __name__ == "__main__":      # child of test_x2y_f2a_fused_backward_vs_oracle: python tests/test_gpu_x2y.py f2a

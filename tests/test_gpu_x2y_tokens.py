@@ -1,5 +1,5 @@
-"""The X2Y attention cores at 65 .. 320 action tokens per video (the wide variants of x2y_core.hip) on the
-GPU against the fp64 oracle, through check_x2y of test_gpu_x2y.py and its tolerances (1e-4 on out, logit,
+"""The X2Y attention cores at 65 .. 320 action tokens per video (the wide variants in x2y_a2f.hip and
+x2y_f2a.hip) on the GPU against the fp64 oracle, through check_x2y of test_gpu_x2y.py and its tolerances (1e-4 on out, logit,
 dX, dY and the positions, 1e-5 on attn, 2e-4 on the weights, each relative to 1 + max|ref|):
 
 * a2f (keys = tokens): one key in a third 32-key block (65), a block edge and one past it (96, 97), 200, 300
@@ -185,10 +185,12 @@ def test_the_fused_core_ran(direction, T, kinds):
     fxf.check_device_status()
 
 
-@pytest.mark.parametrize("direction,nqs,Ts", [("a2f", (300, 97), (700, 413)), ("f2a", (300, 129), (4200, 413))])
+@pytest.mark.parametrize("direction,nqs,Ts", [("a2f", (300, 97), (700, 413)), ("f2a", (300, 129), (4200, 413)),
+                                              ("a2f", (40, 33), (700, 413)), ("f2a", (40, 33), (4200, 413))])
 def test_wide_cores_are_deterministic(direction, nqs, Ts):
     """Two runs of one wide call (several row chunks of the a2f weight-side kernel; the f2a forward at 73
-    chunks, its fused backward in the child process of test_wide_f2a_fused_backward_vs_oracle): every
+    chunks, its fused backward in the child process of test_wide_f2a_fused_backward_vs_oracle), and of the
+    <= 64-row cores with ragged token counts (they share their phase bodies with the wide ones): every
     output and gradient bitwise equal."""
     a = _run_x2y(direction, nqs, Ts, oracle=False)
     b = _run_x2y(direction, nqs, Ts, oracle=False)

@@ -1,5 +1,5 @@
 """Device time of one X2Y map (fx_x2y_fwd / fx_x2y_bwd through fxf.X2YFn) at more than 64 action tokens
-per video: the wide fused cores of x2y_core.hip against the grouped-GEMM path.
+per video: the wide fused cores of x2y_a2f.hip / x2y_f2a.hip against the grouped-GEMM path.
 
 python tools/x2y_tokens_time.py [--iters 30] [--rounds 2] [--out FILE.json] [--commit HASH]
                                 [--step-this BENCH.json] [--step-parent BENCH.json]
