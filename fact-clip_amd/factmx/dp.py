@@ -137,7 +137,8 @@ class DataParallel:
 
     dp = DataParallel(net)                 # broadcast rank 0's weights, flat grad buckets
     dp.zero_grad(); loss = net(...)[0]; loss.backward(); dp.finish_gradients()
-    optimizer over dp.flat (factmx.optim.FusedAdam(..., grad_flat=dp.flat))
+    optimizer over dp.flat (factmx.optim.FusedAdam(..., grad_flat=dp.flat) or FusedSGD, or
+    factmx.optim.build_optimizer(cfg, net.parameters(), grad_flat=dp.flat) for the one cfg names)
     """
 
     def __init__(self, net, group=None, broadcast=True, bucket_mb=256, force_buckets=False):
@@ -351,8 +352,8 @@ class DataParallel:
     def _issue_status(self):
         """All-reduce (MAX) the device status word behind the gradient buckets, on the device: a rank
         whose BiGRU timed out in this backward (invalid gradients, already summed into the buckets) makes
-        EVERY rank's FusedAdam skip the update (fx_adam_step_checked reads the word) and every rank raise
-        at its next read-back, so the replicas neither apply corrupted averages nor diverge."""
+        EVERY rank's FusedAdam or FusedSGD skip the update (fx_adam_step_checked / fx_sgd_step read the word)
+        and every rank raise at its next read-back, so the replicas neither apply corrupted averages nor diverge."""
         if self.world <= 1:
             return
         st = fxf.device_status(self.flat.device)[:1]

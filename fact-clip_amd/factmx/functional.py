@@ -1647,7 +1647,7 @@ def resolve_backward_status(wait=False):
             device_status(dev).zero_()
             raise nx.FactmxNativeError(
                 f"device status {int(h[0])}: {_status_text(int(h[0]))} in the BACKWARD pass of the previous step "
-                "-- its gradients are invalid (a factmx FusedAdam step on them was skipped on the device)")
+                "-- its gradients are invalid (a factmx FusedAdam / FusedSGD step on them was skipped on the device)")
 
 
 def check_device_status(dev=None):

@@ -217,6 +217,7 @@ SIGNATURES = {
     "fx_clip_grad_scale": (I, [P, L, P, F, P]),
     "fx_adam_step": (I, [P, P, P, P, L, L, F, F, F, F, F, F, P, P, P]),
     "fx_adam_step_checked": (I, [P, P, P, P, L, L, F, F, F, F, F, F, P, P, P, P]),
+    "fx_sgd_step": (I, [P, P, P, L, F, F, F, F, P, P, P, P]),
     "fx_loss_workspace_floats": (L, []),
     "fx_class_loss_fwd": (I, [P, L, L, I, I, P, P, P, F, F, P, P, P, P]),
     "fx_class_loss_bwd": (I, [P, L, L, I, I, P, P, P, P, F, F, P, P, P]),

@@ -839,6 +839,19 @@ int fx_adam_step(float* p, float* g, float* m, float* v, long long n, long long 
 int fx_adam_step_checked(float* p, float* g, float* m, float* v, long long n, long long step, float lr,
                          float beta1, float beta2, float eps, float weight_decay, float max_norm,
                          float* workspace, float* norm_out, const int* status, void* stream);
+/* fx_sgd_step: the same tail for cfg.optimizer == "SGD" (scripts/train.py:219-221): optional clipping
+ *   exactly as in fx_adam_step (max_norm > 0: norm computed in-launch into workspace, pre-clip norm to
+ *   norm_out, g scaled and written back only when the coefficient is not 1), then torch.optim.SGD with
+ *   dampening 0, nesterov off, maximize off:
+ *     d = g + weight_decay * p (weight_decay != 0);  buf = momentum * buf + d;  p -= lr * buf
+ *   and, for momentum == 0, p -= lr * d with no buffer at all.  buf is NULL exactly when momentum == 0;
+ *   a zeroed buf gives torch's first step (buf = d).  g keeps the clipped gradient without the decay
+ *   term.  p, g, buf: n floats, 16-byte aligned; momentum >= 0; n == 0 launches nothing.
+ *   status: as in fx_adam_step_checked (non-zero: p, g and buf untouched); NULL: unguarded.
+ *   20 B of HBM traffic per parameter with momentum (24 B when the clip rewrites g), 12 B (16 B) without. */
+int fx_sgd_step(float* p, float* g, float* buf, long long n, float lr, float momentum,
+                float weight_decay, float max_norm, float* workspace, float* norm_out,
+                const int* status, void* stream);
 
 /* ------------------------------------------------------------------------
  * Fused loss terms (fact_clip/models/loss.py); each returns ONE scalar
