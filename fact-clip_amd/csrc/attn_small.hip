@@ -11,6 +11,7 @@
 
 #include "fx_common.h"
 #include "ops.h"
+#include "wave_dev.h"
 
 namespace fx {
 namespace {
@@ -22,17 +23,6 @@ constexpr int SP = SM + 1;    // padded LDS row stride (no bank conflicts on col
 // elements of 64-deep chains (bwd 72 us per launch over only heads x videos = 32 workgroups)
 constexpr int NT = 1024;
 
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wmax(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 constexpr int MAXV = 32;      // videos per launch (the per-video row offsets live in the kernel arguments)
 
 // rows of video v: q / o rows [qo[v], qo[v+1]), k / v rows [ko[v], ko[v+1]) (the host fills v*Lq, v*Lk for
@@ -43,7 +33,7 @@ struct SmallOff {
 };
 
 // keep-scale of probability (head h, global query row qg, global key row kg of ktot): 1/(1-p) or 0 -- the
-// attention-over-T kernels' mask (attn_t.hip drop_keep)
+// attention-over-T kernels' mask (attn_t_dev.h drop_keep)
 __device__ __forceinline__ float keep_scale(unsigned long long seed, unsigned thr, float p, int nh, int h,
                                             unsigned long long qg, unsigned long long kg, unsigned long long ktot) {
   const unsigned long long idx = (qg * nh + h) * ktot + kg;

@@ -29,11 +29,11 @@
 #include <algorithm>
 
 #include "ops.h"
+#include "wave_dev.h"
 
 namespace fx {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int GBM = 64;        // rows per forward tile
 constexpr int GK = 32;         // stage depth

@@ -799,7 +799,7 @@ int fx_decoder_fwd(const fx_decoder_params* p, const float* tgt, long long ldt, 
       // --- cross-attention onto the frames: q = t1 + qpos, k = mem + pos, v = mem (basic.py:504-515)
       const float* tq = t1q ? b + L.t1q : b + L.t1;
       FX_TRY(linear_fwd(tq, A, R, A, p->ca_q_w[l], p->ca_in_b[l], b + L.qc, A, A, 0, s));
-      // every video's tokens over its own frames, all heads, one fused launch (attn_t.hip)
+      // every video's tokens over its own frames, all heads, one fused launch (attn_t_lds.hip, attn_t_rr.hip)
       TAttnOpts o;
       o.koff = p->mem_off;
       o.qoff = p->tok_off;

@@ -4,11 +4,11 @@
 // in the packed order of launch_pack_frag, and the row-tile order on the XCDs.
 #pragma once
 #include "fx_common.h"
+#include "wave_dev.h"
 
 namespace fx {
 namespace frl_dev {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int FR = 32;           // rows per workgroup
 constexpr int FN = 256;          // channels: N of both GEMMs, K of the second
 constexpr int FBK = 32;          // k per stage

@@ -132,8 +132,6 @@ struct Knobs {
   int frl2_min_fill = 55;       // FX_FRL2_MIN_FILL: fused MS-TCN++ layer only when its row tiles cover this % of the CUs (10-layer stack fwd+bwd, fused vs GEMM path: 128 tiles = 50 % 2579 vs 2378 us, 140 tiles = 55 % 2717 vs 3536 us)
   bool aux_stream = true;       // FX_AUX_STREAM=0: the decoder's query-position gradient on the caller's stream
   bool x2y_a2f_dw = true;        // FX_X2Y_A2F_DW=0: the a2f backward's dxv / dxk as grouped split-K GEMMs (A/B)
-  bool tattn_fold = true;        // FX_TATTN_FOLD=0: the register-resident kernels' merge as a second launch (A/B)
-  bool tattn_rr = true;          // FX_TATTN_RR=0: the LDS-staged attention-over-T kernels for head dim 32 too (A/B)
   bool gru_poll2 = true;        // FX_GRU_POLL2=0: one granule poll in flight per lane (A/B)
   int gru_store_wave = 2;        // FX_GRU_STORE_WAVE: GRU forward table stores -- 0 by wave 0's gate threads, 1 staged for a fifth wave, 2 gate threads on the fifth wave (A/B)
   int frl_xcd = 2;             // FX_FRL_XCD: fused MS-TCN layer row tiles on the XCDs -- 0 round robin,

@@ -33,6 +33,7 @@
 // gemm_reduce.hip (split-K reduce, column sums); gemm_plan.h says which family runs which operands.
 #pragma once
 #include "fx_common.h"
+#include "wave_dev.h"
 
 namespace fx {
 
@@ -41,7 +42,6 @@ constexpr int RS = 68;              // [row][k] image stride
 constexpr int CS = 65;              // [k][row] image stride
 constexpr int IMG = BM * RS;        // floats per operand image (>= BK * CS)
 constexpr int NSLOT = 3;            // LDS ring depth
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int WBM = 128;            // rows of the wide (128 x 64) tile
 constexpr int W8T = 512;            // threads of the 8-wave kernels on it
 constexpr int DCH = 32, DMAXW = 8;  // direct kernel: k per chunk, waves per 32x32 tile at most

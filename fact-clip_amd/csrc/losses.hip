@@ -19,23 +19,13 @@
 #include <cmath>
 
 #include "fx_common.h"
+#include "wave_dev.h"
 
 namespace fx {
 namespace {
 
 constexpr int LT = 256;       // threads per block (4 waves, one row per wave at a time)
 constexpr int NBLK = 128;     // row blocks of the forward partial sums
-
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wmax(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
 
 struct Mat {
   const float* p;

@@ -180,7 +180,7 @@ fx_gemm_desc desc_linear_dwdb(const float* dy, long long lddy, const float* x, l
 int linear_bwd_pair(const fx_gemm_desc& dwdb, const fx_gemm_desc& dx, hipStream_t s);
 
 // ---- fused small multi-head attention (attn_small.hip): Lq, Lk, head_dim <= 64 ----
-// drop_p > 0: attention-probability dropout with attn_t.hip's mask (TAttnOpts), probs saved un-dropped
+// drop_p > 0: attention-probability dropout with the attention-over-T mask (TAttnOpts), probs saved un-dropped
 // nvid independent problems stacked by rows (video v: q/o rows v*Lq.., k/v rows v*Lk..);
 // probs (nvid, nhead, Lq, Lk) saved; o (Lq, nhead*hd) with row stride ldo.
 // off (host, nvid + 1 row offsets from 0, self-attention): video v owns q/o and k/v rows [off[v], off[v+1]);
@@ -196,7 +196,7 @@ int launch_mha_small_bwd(const float* q, long long ldq, const float* k, long lon
                          long long lddv, hipStream_t s, int nvid = 1, float drop_p = 0.f, unsigned long long seed = 0,
                          const int* off = nullptr);
 
-// ---- fused multi-head attention of queries over T frames (attn_t.hip) ---------------------
+// ---- fused multi-head attention of queries over T frames (attention.cpp, attn_t_lds.hip, attn_t_rr.hip) ----
 // nvid videos stacked by rows (queries v*Qv.., keys/values v*Tv.. or opt->koff); head h = columns
 // [h*hd, h*hd+hd) of q/k/v/o.  fwd writes o and lse (nvid, nhead, Qv); bwd writes (or with acc_kv adds)
 // dk, dv (rows: one per key) and writes dq.  More than 64 queries run as blocks of 64.

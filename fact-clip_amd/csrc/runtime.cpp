@@ -141,9 +141,7 @@ const Knobs& knobs() {
     if (const char* p = env("FX_AUX_STREAM")) k.aux_stream = p[0] != '0';
     if (const char* p = env("FX_GRU_POLL2")) k.gru_poll2 = p[0] != '0';
     if (const char* p = env("FX_GRU_STORE_WAVE")) k.gru_store_wave = std::max(0, std::min(2, std::atoi(p)));
-    if (const char* p = env("FX_TATTN_RR")) k.tattn_rr = p[0] != '0';
     if (const char* p = env("FX_X2Y_A2F_DW")) k.x2y_a2f_dw = p[0] != '0';
-    if (const char* p = env("FX_TATTN_FOLD")) k.tattn_fold = p[0] != '0';
     if (const char* p = env("FX_X2Y_FUSED")) k.x2y_fused = p[0] != '0';
     if (const char* p = env("FX_X2Y_F2A_BWD")) k.x2y_f2a_bwd = std::atoi(p);
     if (const char* p = env("FX_X2Y_F2A_ONE")) k.x2y_f2a_one = p[0] != '0';

@@ -40,35 +40,15 @@
 #include "fx_common.h"
 #include "ops.h"
 #include "tokdec.h"
+#include "wave_dev.h"
 
 namespace fx {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float v4f __attribute__((ext_vector_type(4)));
 constexpr int TT = 256;                 // threads per workgroup (4 waves)
 constexpr int HS = 33;                  // self-attention LDS row stride (head dim 32 + 1)
 
-// ------------------------------------------------------------------ write-through (sc1) accesses
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7fffffff, 0x00020000);
-}
-// (cache-policy operand 16 = sc1 on gfx950: L1 bypassed, stores written through)
-__device__ __forceinline__ float4 ldc4(const float* base, long long idx) {
-  const v4f v = __builtin_amdgcn_raw_buffer_load_b128(rsrc(base), (int)(idx * 4), 0, 16);
-  return make_float4(v[0], v[1], v[2], v[3]);
-}
-// (the b32 forms move 32-bit integers: the float's bits, not its value)
-__device__ __forceinline__ float ldc1(const float* base, long long idx) {
-  return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc(base), (int)(idx * 4), 0, 16));
-}
-__device__ __forceinline__ void stc1(float* base, long long idx, float v) {
-  __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rsrc(base), (int)(idx * 4), 0, 16);
-}
-__device__ __forceinline__ void stc4(float* base, long long idx, float4 v) {
-  v4f x = {v.x, v.y, v.z, v.w};
-  __builtin_amdgcn_raw_buffer_store_b128(x, rsrc(base), (int)(idx * 4), 0, 16);
-}
+// (the write-through (sc1) accesses ldc1 / ldc4 / stc1 / stc4: wave_dev.h)
 // plain accesses to tensors written before the launch, as global-memory instructions (the phase fields
 // come through LDS, so the compiler cannot tell that their pointers are global and would emit flat ones)
 // (through the native vector type: float4's copy constructor would take the operand back to a generic
@@ -85,16 +65,6 @@ __device__ __forceinline__ void st1(float* p, float v) { *(gf1*)(p) = v; }
 __device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 __device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wmax(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
 // sum over the 8 lanes of one staged row (consecutive lanes)
 __device__ __forceinline__ float rsum8(float v) {
   v += __shfl_xor(v, 1, 64);
@@ -102,15 +72,9 @@ __device__ __forceinline__ float rsum8(float v) {
   v += __shfl_xor(v, 4, 64);
   return v;
 }
-__device__ __forceinline__ void zero16(f32x16& a) {
-#pragma unroll
-  for (int i = 0; i < 16; ++i) a[i] = 0.f;
-}
 __device__ __forceinline__ float keepf(unsigned long long seed, unsigned thr, float scale, unsigned long long idx) {
   return fx_drop_bits(seed, idx) >= thr ? scale : 0.f;
 }
-// accumulator element r of a lane: row (r & 3) + 8 (r >> 2) + 4 (lane >> 5), column lane & 31
-__device__ __forceinline__ int acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
 // workgroup barrier for LDS hand-offs only: waits for this wave's LDS accesses, not for its global
 // stores (__syncthreads() also waits for every outstanding global store -- with write-through stores,

@@ -385,7 +385,7 @@ __global__ __launch_bounds__(DWT) void x2y_a2f_dw_kernel(A2fDwArgs a) {
     if (direct) {
       if (x < nx && t < nxt) out[(long long)(x0 + xb + x) * a.Hd + d] = v8[i] * mul;
     } else {
-      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v8[i]), x2y_rsrc(part), e * 4, 0, 16);
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v8[i]), rsrc(part), e * 4, 0, 16);
     }
   }
   if (direct) return;
@@ -406,7 +406,7 @@ __global__ __launch_bounds__(DWT) void x2y_a2f_dw_kernel(A2fDwArgs a) {
 #pragma unroll
     for (int i = 0; i < 8; ++i)
       x8[q][i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
-          x2y_rsrc(pbase), ((long long)min(q, nch - 1) * 2048 + tid + i * DWT) * 4, 0, 16));
+          rsrc(pbase), ((long long)min(q, nch - 1) * 2048 + tid + i * DWT) * 4, 0, 16));
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     const int e = tid + i * DWT, t = e >> 10, r = (e >> 6) & 15, l = e & 63;

@@ -1,18 +1,18 @@
 // Device pieces shared by the fused X2Y attention cores (x2y_a2f.hip: frames attend to the action tokens,
 // x2y_f2a.hip: tokens attend to the frames): the per-video table of a launch and its lookup, the two tile
 // products on v_mfma_f32_32x32x2_f32 (rows x keys over an Hd slice; LDS rows x chunk keys -> Hd column
-// tiles), the wave-order sum of partial tiles through LDS, the write-through buffer resource and the grid
-// barrier of the one-launch backward.
+// tiles), the wave-order sum of partial tiles through LDS and the grid barrier of the one-launch backward
+// (the write-through buffer resource `rsrc` of the partials is wave_dev.h's).
 #pragma once
 #include "fx_common.h"
 #include "ops.h"
+#include "wave_dev.h"
 
 #include <algorithm>
 
 namespace fx {
 namespace x2y_dev {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int XR = 32;            // a2f: query rows per workgroup
 constexpr int XT = 512;           // threads (8 waves)
 constexpr int XMAXK = 64;         // a2f: keys per video (the wide variant: FX_X2Y_MAXTOK)
@@ -208,11 +208,6 @@ __device__ __forceinline__ void keys_out(const float (*L)[FC + 1], const float* 
 }
 
 // ---------------------------------------------------------------- hand-offs between workgroups
-// write-through (sc1, aux 16) buffer access for partials another workgroup reads in the same launch
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t x2y_rsrc(const void* p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7fffffff, 0x00020000);
-}
-
 // Grid barrier of the one-launch form (every workgroup co-resident: the grid is capped by the occupancy
 // calculator on the host): each workgroup's write-through stores acknowledged (vmcnt 0) before its arrival;
 // every workgroup counts its exit, timed out or not, and the last one re-arms the slot.  Bounded spin: a

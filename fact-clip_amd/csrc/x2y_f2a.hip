@@ -246,7 +246,7 @@ __device__ __forceinline__ void f2ab_dp_phase(const F2aBwdArgs& a, const F2aChun
     for (int o = 4; o >= 1; o >>= 1) part += __shfl_xor(part, o, 8);
     if (c8 == 0 && row < ny) {
       const long long si = ((long long)c.chunk * qrows + q0 + row) * 2;
-      if (PASS == 3) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(part), x2y_rsrc(a.stats), (int)(si * 4), 0, 16);
+      if (PASS == 3) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(part), rsrc(a.stats), (int)(si * 4), 0, 16);
       else a.stats[si] = part;
     }
   }
@@ -266,7 +266,7 @@ __device__ __forceinline__ void f2ab_rowdot(const F2aBwdArgs& a, const F2aChunk&
   if (tid < ny)
     for (int ch = 0; ch < nch; ++ch) {
       const long long si = ((long long)(c.c0 + ch) * qrows + q0 + tid) * 2;
-      if (PASS == 3) sum += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(x2y_rsrc(a.stats), (int)(si * 4), 0, 16));
+      if (PASS == 3) sum += __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc(a.stats), (int)(si * 4), 0, 16));
       else sum += a.stats[si];
     }
   rdot[tid] = sum;

@@ -8,7 +8,7 @@ each attention core's edge:
 
 * the LDS-resident small attention (attn_small.hip): a one-token video, a 64-token one;
 * the persistent token kernel (tokdec.hip): 32 / 1 / 17 tokens, fx_prof kind 8 proves it ran;
-* more than 64 tokens (attn_t.hip in query blocks of 64): 70 and 3 tokens -- the second query block has
+* more than 64 tokens (attn_t_lds.hip in query blocks of 64): 70 and 3 tokens -- the second query block has
   no query of the short video -- at head dim 8 and 32;
 * the register-resident head-dim-32 cross attention with ragged queries and ragged memory;
 * tok_off of an even split is bitwise tok_off = None; dropout masks are indexed by global stacked rows

@@ -1,6 +1,6 @@
 """Diagnostic: where one attention-over-T forward launch (tattn_fwd32_kernel, the headline shape: 2 videos,
 32 queries, T = 4096, head dim 32, 8 heads; 16 chunks of 256 keys per (video, head) = 256 workgroups) spends its
-time, from s_memrealtime stamps of thread 0 of every workgroup (diagnostic build: attn_t.hip with
+time, from s_memrealtime stamps of thread 0 of every workgroup (diagnostic build: attn_t_rr.hip with
 -DTATTN_STAMPS, loaded through FACTMX_LIB).  Stamps: 0 start, 1 loads + S = q K^T done, 2 P V done and the wave
 partials in LDS, 3 the chunk partial stored (issued), 4 its stores acknowledged, 5 arrival counted, 6 merge done
 (the last arriver of each (video, head) only)."""
